@@ -10,7 +10,13 @@ Default workload: BASELINE.json configs[3] = C4, the 50,000-vertex / 500,000-edg
 synthetic AS graph, all 50,000 vertices attached: the full 50k x 50k latency and
 reliability table (2.5e9 pairs, 40 GB of f64 in HBM) per step.  --config c2 / c3
 select the smaller configs, --config c5 the dense complete graph (K3 direct fill + K5,
-with the K4 Floyd-Warshall timed beside it).
+with the K4 Floyd-Warshall timed beside it under --full).
+
+A plain run sets up, warms up, times --steps steps and prints the result line (value,
+ms_per_step).  --full adds everything else: a second pass of the same steps with HIP events
+around the rows kernel (kernel_ms, roofline, PMC traffic), the oracle spot checks (--verify),
+the CPU baselines, the collective split (N>1) and the K4 timings (c5).  --dump-outputs DIR
+writes what the last timed step computed (lat, rel, row_min, runahead_min) as DIR/<name>.npy.
 
 Multi-GPU (one process per GPU, launched by torch.distributed.run):
   --scaling strong (default) one topology, attached sources sharded over the ranks
@@ -228,6 +234,67 @@ def timed(fn, reps, sync, barrier=None):
     return time.perf_counter() - t0
 
 
+DUMP_SAMPLE = 3_000_000  # elements of lat and of rel kept from a table too large to dump whole
+DUMP_WHOLE_BYTES = 48 << 20  # lat + rel are written whole up to this size (64 MB is the ceiling in all)
+
+
+def dump_outputs(out_dir, torch, rank, world, rows, d_lat, d_rel, d_rmin, d_min):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as f64
+    .npy files: the latency and reliability tables (`rows` x targets), each row's minimum
+    and the runahead min.  Tables above DUMP_WHOLE_BYTES are written as the same
+    DUMP_SAMPLE flat positions of both (seed 2024, sorted), so two builds run with the
+    same arguments write comparable arrays."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    lat, rel = d_lat[:rows].reshape(-1), d_rel[:rows].reshape(-1)
+    if 16 * lat.numel() > DUMP_WHOLE_BYTES:
+        idx = np.sort(np.random.default_rng(2024).choice(lat.numel(), size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(lat.device)
+        lat, rel = lat[idx], rel[idx]
+    out = {"lat": lat, "rel": rel, "row_min": d_rmin[:rows], "runahead_min": d_min}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), t.cpu().numpy().astype(np.float64, copy=False))
+
+
+def add_kernel_figures(res, args, eng, plan, g, ns, nt, kms, lms):
+    """--full: what the kernel-timing pass measured (kms / lms: per-step HIP-event times of
+    the rows launch and of the landmark part before it) and the roofline built on it."""
+    n, nnz = g.n, g.nnz
+    kavg_s = float(np.mean(kms)) / 1e3
+    peak = 8000.0
+    # roofline: the bytes the launch MUST move (its output rows, 16 B per pair) over the
+    # kernel's HIP-event time; the counters' bytes beside it (traffic, traffic_frac)
+    out_bytes = 16.0 * ns * nt
+    achieved = out_bytes / kavg_s / 1e9
+    kname = {0: "sssp_rows_kernel", 1: "sssp_k32_kernel",
+             2: ("sssp_batch_rows_kernel" if eng.info["reserved"] == 1 else "sssp_batch_kernel"),
+             4: "sssp_delta_kernel", 5: "sssp_f64d_kernel"}.get(eng.info["kernel"], str(eng.info["kernel"]))
+    phys = physical(args.config, ns, nt, kavg_s, peak, kname)
+    model_bytes = ns * b_src(n, nnz, nt)
+    res["kernel_ms"] = float(np.mean(kms))
+    res["landmark_ms"] = float(np.mean(lms))
+    res["roofline"] = {
+        "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
+        "traffic": phys.get("traffic_bytes"),
+        "traffic_frac": phys.get("traffic_frac"),
+        "kernel": kname,
+        "model": "compulsory bytes per launch = the lat + rel output rows (16 B per source-target pair); "
+                 "achieved = those bytes / the rows kernel's HIP-event time; traffic = PMC HBM bytes per "
+                 "launch (profiles/), traffic_frac = traffic / kernel time / peak",
+        "compulsory_bytes_per_launch": out_bytes,
+        "launches_per_step": plan.info["launches"],
+        "physical": phys,
+        "work_avoided": {
+            "survey_model": "SURVEY 8(d) B_src = 4(n+1) + 12 nnz + 12 n + 16 |T| per source row "
+                            "(every row a full CSR pass)",
+            "bytes_per_source": b_src(n, nnz, nt),
+            "model_rate_GBps": model_bytes / kavg_s / 1e9,
+            "model_over_peak": model_bytes / kavg_s / 1e9 / peak,
+            "note": "above 1 means seeded rows skip most of the per-row CSR pass the model charges; "
+                    "it measures work avoided, not bandwidth used"},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,7 +312,15 @@ def main():
     ap.add_argument("--no-seed", action="store_true", help="plain KD rows (no seeded plan)")
     ap.add_argument("--emulate", default="", help="W:R = one GPU runs rank R's plan of a W-GPU strong split "
                     "(diagnostic: that rank's compute time; no collectives)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the kernel-timing pass (kernel_ms, roofline, "
+                         "PMC traffic), the oracle spot checks (--verify), the CPU baselines, the collective "
+                         "split (N>1) and the K4 Floyd-Warshall timings (c5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (f64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.kernel != "auto":
         os.environ["SHD_ROUTE_KERNEL"] = args.kernel
     if args.no_seed:
@@ -334,9 +409,10 @@ def main():
     d_min = torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
 
-    l_start = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    k_start = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    k_end = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+    n_ev = args.steps if args.full else 0  # (the kernel-timing pass is --full only)
+    l_start = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev)]
+    k_start = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev)]
+    k_end = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev)]
 
     def gather_tables():
         if ns:
@@ -373,16 +449,18 @@ def main():
     eng.sync(sh)
     dt = timed(step, args.steps, torch.cuda.synchronize, barrier)
     eng.sync(sh)  # raises on any device-side error
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, rank, world, ns, d_lat, d_rel, d_rmin, d_min)
     # dominant-kernel duration: HIP events on the launch stream around the rows launch, in
     # a second pass of the same K steps (the throughput pass above carries no events)
-    for t in range(args.steps):
+    for t in range(n_ev):
         step(t)
     torch.cuda.synchronize()
     eng.sync(sh)
-    kms = [k_start[t].elapsed_time(k_end[t]) for t in range(args.steps)]
-    lms = [l_start[t].elapsed_time(k_start[t]) for t in range(args.steps)]  # (0 unless landmark-only)
+    kms = [k_start[t].elapsed_time(k_end[t]) for t in range(n_ev)]
+    lms = [l_start[t].elapsed_time(k_start[t]) for t in range(n_ev)]  # (0 unless landmark-only)
     split = None
-    if gather:
+    if gather and args.full:
         # compute / collective split: the runahead all-reduce and the table
         # all-gather, each timed on its own
         ar_s = timed(lambda: runahead_min(d_min, dist), 20, torch.cuda.synchronize, barrier) / 20
@@ -416,7 +494,7 @@ def main():
 
     # correctness spot check against the oracle, outside the timed region
     verified = None
-    if args.verify and rank == 0 and ns:
+    if args.full and args.verify and rank == 0 and ns:
         from oracle.oracle import OracleGraph, TIE_MINKEY
         og = OracleGraph(g)
         pick = np.linspace(0, ns - 1, num=min(args.verify, ns)).astype(int)
@@ -432,17 +510,6 @@ def main():
         return
 
     n, nnz = g.n, g.nnz
-    kavg_s = float(np.mean(kms)) / 1e3
-    peak = 8000.0
-    # roofline: the bytes the launch MUST move (its output rows, 16 B per pair) over the
-    # kernel's HIP-event time; the counters' bytes beside it (traffic, traffic_frac)
-    out_bytes = 16.0 * ns * nt
-    achieved = out_bytes / kavg_s / 1e9
-    kname = {0: "sssp_rows_kernel", 1: "sssp_k32_kernel",
-             2: ("sssp_batch_rows_kernel" if eng.info["reserved"] == 1 else "sssp_batch_kernel"),
-             4: "sssp_delta_kernel", 5: "sssp_f64d_kernel"}.get(eng.info["kernel"], str(eng.info["kernel"]))
-    phys = physical(args.config, ns, nt, kavg_s, peak, kname)
-    model_bytes = ns * b_src(n, nnz, nt)
     res = {
         "metric": "source-paths/sec",
         "build_id": build_id(),
@@ -470,34 +537,12 @@ def main():
         },
         "gteps": total_src * g.m_nonloop * args.steps / dt / 1e9,
         "pairs_per_s": total_src * nt * args.steps / dt,
-        "kernel_ms": float(np.mean(kms)),
-        "landmark_ms": float(np.mean(lms)),
         "step_contents": (("this rank's share of the landmark rows + their all-gather over the ranks + the job records "
                            "(1 kernel) + the rows launch + runahead min" if lm_split else
                            "landmark rows (hub-row launch) + the job records derived from them (1 kernel) + the "
                            "rows launch + runahead min: every SSSP of the table") if plan.info["launches"] > 1 else
                           "the rows launch (every row of the table) + runahead min"),
         "time_to_table_ms": t_plan * 1e3 + dt / args.steps * 1e3,
-        "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
-            "traffic": phys.get("traffic_bytes"),
-            "traffic_frac": phys.get("traffic_frac"),
-            "kernel": kname,
-            "model": "compulsory bytes per launch = the lat + rel output rows (16 B per source-target pair); "
-                     "achieved = those bytes / the rows kernel's HIP-event time; traffic = PMC HBM bytes per "
-                     "launch (profiles/), traffic_frac = traffic / kernel time / peak",
-            "compulsory_bytes_per_launch": out_bytes,
-            "launches_per_step": plan.info["launches"],
-            "physical": phys,
-            "work_avoided": {
-                "survey_model": "SURVEY 8(d) B_src = 4(n+1) + 12 nnz + 12 n + 16 |T| per source row "
-                                "(every row a full CSR pass)",
-                "bytes_per_source": b_src(n, nnz, nt),
-                "model_rate_GBps": model_bytes / kavg_s / 1e9,
-                "model_over_peak": model_bytes / kavg_s / 1e9 / peak,
-                "note": "above 1 means seeded rows skip most of the per-row CSR pass the model charges; "
-                        "it measures work avoided, not bandwidth used"},
-        },
         "plan": {**plan.info, "plan_seconds": t_plan},
         "landmark_split": ({**plan.landmarks(), "exchange_bytes_per_rank": (world - 1) * -(-plan.landmarks()["nland"] // ew)
                             * plan.landmarks()["row_stride"] * 6 if world > 1 else None,
@@ -507,7 +552,10 @@ def main():
                             if world == 1 else "exchange inside the step"} if lm_split else None),
         "runahead_min_latency_ms": runahead,
         "verified_rows_vs_oracle": verified,
+        "full": bool(args.full),
     }
+    if args.full:
+        add_kernel_figures(res, args, eng, plan, g, ns, nt, kms, lms)
     if split is not None:
         c_s, ar_s, ag_s = (float(x) for x in split.tolist())
         gb = (world - 1) * seg * ((2 if lat16 else 8) + 8)  # received per GPU
@@ -522,7 +570,7 @@ def main():
                         "payload_over_full_table": gb / full_gb,
                         "allgather_GBps_per_gpu": (gb / ag_s / 1e9) if ag_s else None,
                         "gathered_rows_verified_vs_oracle": gathered_ok}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         par, faithful = cpu_baseline(g, all_sources, targets, args.cpu_budget)
         res["cpu_baseline"] = par
         res["cpu_baseline_faithful"] = faithful
@@ -605,6 +653,23 @@ def bench_c5(args, torch, dist, world, rank, dev, barrier):
     eng.sync(sh)
     dt = timed(step, args.steps, torch.cuda.synchronize, barrier)
     eng.sync(sh)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, rank, world, n, d_lat, d_rel, d_rmin, d_min)
+    res = {
+        "metric": "source-paths/sec", "build_id": build_id(), "value": n * args.steps / dt, "unit": "source-paths/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{g.name}: complete K{n} + self-loops, reference semantics = every pair DIRECT "
+                               "(K3) + runahead min (K5) (BASELINE.json configs[4])",
+                   "n_vertices": n, "n_edges": g.m, "sources_total": n, "targets": n, "parallelism": "one GPU"},
+        "pairs_per_s": n * n * args.steps / dt,
+        "runahead_min_latency_ms": float(d_min.item()), "verified_rows_vs_oracle": None, "cpu_baseline": None,
+        "full": bool(args.full),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(stream)
     for _ in range(args.steps):
@@ -612,7 +677,6 @@ def bench_c5(args, torch, dist, world, rank, dev, barrier):
     e1.record(stream)
     torch.cuda.synchronize()
     k3_s = e0.elapsed_time(e1) / 1e3 / args.steps
-    runahead = float(d_min.item())
     verified = None
     if args.verify and rank == 0:
         from oracle.oracle import OracleGraph
@@ -656,14 +720,7 @@ def bench_c5(args, torch, dist, world, rank, dev, barrier):
     # 35.8 T packed instructions/s (u32 adds 50.0 T/s), the roof the kernel can reach
     peak_nominal = 256 * 4 * 32 * 2.4e9
     peak_relax = 35.8e12
-    res = {
-        "metric": "source-paths/sec", "build_id": build_id(), "value": n * args.steps / dt, "unit": "source-paths/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"{g.name}: complete K{n} + self-loops, reference semantics = every pair DIRECT "
-                               "(K3) + runahead min (K5) (BASELINE.json configs[4])",
-                   "n_vertices": n, "n_edges": g.m, "sources_total": n, "targets": n, "parallelism": "one GPU"},
-        "pairs_per_s": n * n * args.steps / dt,
+    res.update({
         "kernel_ms": k3_s * 1e3,
         "roofline": {"bound": "hbm", "achieved": 32.0 * n * n / k3_s / 1e9, "peak": 8000.0, "unit": "GB/s",
                      "frac": 32.0 * n * n / k3_s / 1e9 / 8000.0, "traffic": k3_phys.get("traffic_bytes"),
@@ -678,8 +735,8 @@ def bench_c5(args, torch, dist, world, rank, dev, barrier):
                "fp64_equivalent_peak_grelax_per_s": 39.3e12 / 1e9,
                "fw_rows_ms": fwr_s * 1e3, "rows_verified_vs_oracle": fw_ok,
                "fw_plus_rows_source_paths_per_s": n / (fw_s + fwr_s)},
-        "runahead_min_latency_ms": runahead, "verified_rows_vs_oracle": verified, "cpu_baseline": None,
-    }
+        "verified_rows_vs_oracle": verified,
+    })
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"], res["cpu_baseline_fw"] = cpu_baseline_c5(g, T, args.cpu_budget)
     print(json.dumps(res), flush=True)

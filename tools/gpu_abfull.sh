@@ -14,7 +14,7 @@ i=0
 for cfg in ${CFGS:-c4 c3}; do
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 300 python -u bench.py --config $cfg --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --verify 4 \
+    env $v timeout -k 10 300 python -u bench.py --full --config $cfg --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --verify 4 \
         > gpurun_out/abf_$i.json 2> gpurun_out/abf_$i.err || { echo "variant [$v] $cfg failed"; tail -5 gpurun_out/abf_$i.err; exit 1; }
     python -c "import json;d=json.load(open('gpurun_out/abf_$i.json'));print('$cfg [$v]', 'ms/step', round(d['ms_per_step'],3), 'kernel_ms', round(d['kernel_ms'],3), 'verified', d['verified_rows_vs_oracle'])"
   done

@@ -23,7 +23,7 @@ tests)
   ;;
 bench)
   for cfg in ${CFGS:-c4 c3 c2 c5 c3f c2f c4f}; do
-    extra=""; steps=20
+    extra="--full"; steps=20  # (kernel_ms, roofline, verification and the CPU baselines are --full only)
     [ $cfg = c4f ] && steps=3
     SHD_ROUTE_PLAN_DEBUG=1 timeout -k 10 500 python -u bench.py --config $cfg --steps $steps --warmup 5 $extra \
         > gpurun_out/${TAG}_bench_$cfg.json 2> gpurun_out/${TAG}_bench_$cfg.err || { echo BENCH $cfg FAILED; tail gpurun_out/${TAG}_bench_$cfg.err; exit 1; }

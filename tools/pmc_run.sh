@@ -6,6 +6,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 tag=$1; shift
+BENCH_ARGS="--full $BENCH_ARGS"  # (the kernel-timing pass's launches are profiled too, as before --full)
 run() {  # name counters...
   local name=$1; shift
   timeout -s KILL 90 rocprofv3 --pmc "$@" -d gpurun_out/pmc_${tag}/${name} -o run --output-format csv \
