@@ -10,7 +10,8 @@
  * (with its plans) runs one rows launch at a time: the launches of shd_route_rows_async
  * and shd_route_rows_planned_async share the context's work-queue counter and
  * per-workgroup scratch, so two of them must not be in flight together (enqueue them
- * on one stream, or synchronise in between).
+ * on one stream, or synchronise in between).  The path hops calls (shd_route_hops*,
+ * shd_route_paths) run a rows launch inside and fall under the same rule.
  *
  * Reference interface each entry point replaces (file:line in the reference):
  *   shd_route_create   <- _topology_loadGraph/_topology_checkGraph/_topology_extractEdgeWeights
@@ -21,6 +22,9 @@
  *                         batched over many sources; with SHD_ROUTE_DISPATCH also the
  *                         direct-path dispatch of _topology_getPathEntry (topology.c:2019-2031)
  *                         and _topology_lookupDirectPath (topology.c:1877-1927)
+ *   shd_route_hops, shd_route_paths <- the path itself: the vertex sequence igraph returns
+ *                         (topology.c:1756) and the per-hop walk that logs it
+ *                         (topology.c:1449, 1502-1503, 1829-1844)
  *   shd_route_direct   <- _topology_lookupDirectPath (topology.c:1877-1927) for many pairs
  *   shd_route_self     <- _topology_computeShortestPathToSelf (topology.c:1545-1653)
  *   shd_route_min_reduce <- minimumPathLatency tracking (topology.c:1374-1385)
@@ -129,6 +133,53 @@ int shd_route_rows_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns,
 
 /* Wait for `stream` and return the first device-side error raised since the last sync. */
 int shd_route_sync(shd_route_t* ctx, void* stream);
+
+/* ---- path hops: hop counts and explicit routes of the chosen paths ---------------------
+ * The path behind every number above, which the reference shows in the line
+ * _topology_computeSourcePaths logs per target (topology.c:1449, 1502-1503, 1829-1844).
+ * Entries are those of shd_route_rows, same flags:
+ *   t != s : hops = the edges on the chosen shortest path (the tie rule above); the path is
+ *            hops + 1 vertices from s to t with hops edge ids.
+ *   t == s : the batch self entry (topology.c:1471-1499): hops = 1, vertices [s, s], the edge
+ *            the self-loop; without a self-loop the entry is -1 and SHD_ROUTE_ENOEDGE.
+ *   unreachable t : entry -1 and SHD_ROUTE_EUNREACH.
+ * Failed entries never stop the rest from being written; the code is returned at the end
+ * (shd_route_hops, shd_route_paths) or by the next shd_route_sync (shd_route_hops_async).
+ * With SHD_ROUTE_DISPATCH a complete graph, or prefer-direct with an adjacent pair, gives the
+ * one-hop direct path [s, t] (topology.c:1877-1927, 2019-2031) over the edge the direct
+ * tables keep, the lowest edge id joining the pair; without the flag always the tree path.
+ * On a multigraph (info.multigraph, SURVEY hazard H3) the edge reported for a tree hop is the
+ * tie rule's: the lowest edge id among the parallel edges that are tight for that hop, which
+ * is the edge the latency came from; the reference's igraph_get_eid may name another one.
+ * The hops calls derive everything from the all-vertex latency rows of shd_route_rows_async,
+ * so they work with every kernel the context selects, and they use the context's scratch and
+ * its rows launch: the "one rows launch at a time" rule at the top of this header covers
+ * them too (no rows, planned rows or hops call of the same context in flight together).
+ * Scratch: per source of a chunk an f64 distance row and a u32 parent row over all vertices
+ * (shd_route_paths: an i32 hop row too), chunks of sources sized to 1 GiB, or to
+ * SHD_ROUTE_HOPS_SCRATCH bytes from the environment.  SHD_ROUTE_HOPS_LDS=0 keeps the hop
+ * counting's state out of LDS (its large-graph form, for tests).  Diagnostic rate: every
+ * call runs the sources' SSSP again. */
+
+/* d_hops[i*ld + j] = hops of src[i] -> tgt[j] (i32, -1 = failed entry), d_row_max[i] = the
+ * largest entry of row i; either may be NULL.  Device pointers, as shd_route_rows_async. */
+int shd_route_hops_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                         int32_t nt, int64_t ld, uint32_t flags, int32_t* d_hops, int32_t* d_row_max,
+                         void* stream);
+/* Same with host pointers (row stride nt); blocks. */
+int shd_route_hops(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                   uint32_t flags, int32_t* hops_out, int32_t* row_max_out);
+/* Explicit routes of npairs (pair_src[k], pair_tgt[k]) pairs, in any order, repeats allowed
+ * (grouped by source inside).  Host pointers; blocks.  off_out (npairs + 1 entries):
+ * off_out[k] = the element offset of pair k's vertices in vert_out, off_out[k+1] - off_out[k]
+ * = its hops + 1, or 0 for a failed pair.  The edge ids of pair k start in edge_out at
+ * off_out[k] - (the pairs before k that did not fail), i.e. at off_out[k] - k when none
+ * failed.  cap = the elements vert_out and edge_out can each hold: if cap is smaller than
+ * off_out[npairs] the call returns SHD_ROUTE_EINVAL with off_out complete and nothing
+ * written to vert_out / edge_out, and the caller retries with that size (vert_out NULL and
+ * cap 0: the sizing call).  A vertex out of range is SHD_ROUTE_EINVAL for the whole call. */
+int shd_route_paths(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs,
+                    uint32_t flags, int64_t* off_out, int32_t* vert_out, int32_t* edge_out, int64_t cap);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

@@ -113,6 +113,41 @@ uint64_t shd_topology_triangle_bytes(shd_topology_t* top);
 /* _topology_logAllCachedPaths (topology.c:1929-1967): one line per cached Path. */
 int shd_topology_dump_paths(shd_topology_t* top, FILE* out);
 
+/* ---- the routes behind the cached Paths ------------------------------------------------
+ * What _topology_computeSourcePaths logs for every path it computes (topology.c:1829-1844):
+ *   shortest path A<-->B (i<-->j) is L ms with P loss, path: A<--[lat,loss]-->X<--[lat,loss]-->B
+ * ("-->" and "--" on directed graphs; names are graphml ids, or decimal vertex indices for
+ * shd_topology_new_from_graph topologies, as in shd_topology_dump_paths).  These calls run
+ * on engine 0 under the topology lock (shd_route_paths: the sources' SSSP again), compute on
+ * demand and cache nothing: diagnostic rate, not per packet.  They change neither the fill
+ * nor the cache nor what any accessor above returns. */
+
+/* The route of the stored Path of {src, dst}, in the stored orientation (from the lower
+ * attached vertex to the higher, as shd_topology_is_direct_path takes it): hops + 1
+ * vertices into vert and hops edge ids into edge when cap >= hops + 1 (else nothing is
+ * written).  Returns hops, or -1 as the getters do (not attached, never stored) and for a
+ * self pair without a self-loop, whose stored Path is the path to self
+ * (topology.c:1545-1653), not a route of the graph's edges. */
+int32_t shd_topology_get_path(shd_topology_t* top, int32_t src, int32_t dst, int32_t* vert, int32_t* edge,
+                              int32_t cap);
+/* The line above for that Path into buf (snprintf-style: at most len - 1 characters and a
+ * NUL; returns the full length, -1 on error). */
+int shd_topology_format_path(shd_topology_t* top, int32_t src, int32_t dst, char* buf, size_t len);
+/* One such line per cached pair that came from source paths, in triangle order (the order
+ * of shd_topology_dump_paths): direct-dispatch pairs (topology.c:2019-2031) and self pairs
+ * resolved as the path to self are left out.  Routes are fetched a block of source rows at
+ * a time. */
+int shd_topology_dump_routes(shd_topology_t* top, FILE* out);
+/* The formatter alone, a pure host function (route_fmt.c): vert = the nv >= 1 vertices of
+ * the path, hop_lat / hop_rel = latency and reliability of its nv - 1 edges, lat / rel =
+ * the Path's totals, names = graphml ids indexed by vertex (NULL, or a NULL entry: the
+ * decimal index).  The text goes to *buf, a malloc buffer of *cap bytes (NULL / 0 to
+ * start) that is grown with realloc and stays the caller's to free; returns its length
+ * without the NUL, -1 on a bad argument or allocation failure. */
+int64_t shd_topology_route_line(char** buf, size_t* cap, char* const* names, const int32_t* vert, int32_t nv,
+                                const double* hop_lat, const double* hop_rel, double lat, double rel,
+                                int directed);
+
 #ifdef __cplusplus
 }
 #endif

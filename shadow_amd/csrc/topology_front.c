@@ -582,6 +582,146 @@ uint64_t shd_topology_runahead_ns(shd_topology_t* t) {
     return ns > 0 ? ns : 10ull * 1000000ull;              /* master.c:138 */
 }
 
+/* ---- the routes behind the cached Paths (shd_route_paths on engine 0, nothing cached) ---- */
+
+/* the dispatch of the stored pair a <= b (topology.c:2019-2031), as is_direct_path */
+static inline int pair_direct(const shd_topology_t* t, int32_t a, int32_t b) {
+    return t->complete || (t->prefer_direct && adjacent(t, a, b));
+}
+
+/* route of the stored Path of {s, d}: hops, *vp / *ep malloc'd (hops + 1 vertices, hops
+ * edge ids); -1 without a route */
+static int32_t route_of(shd_topology_t* t, int32_t s, int32_t d, int32_t** vp, int32_t** ep, pcache** cp,
+                        int32_t* ip, int32_t* jp) {
+    if (entry_ij(t, s, d, cp, ip, jp) < 0) return -1;
+    const int32_t a = s < d ? s : d, b = s < d ? d : s;  /* stored orientation: min -> max */
+    const int64_t cap = (int64_t)t->n + 1;               /* a path visits a vertex once ([a, a]: 2) */
+    int32_t* vert = malloc(sizeof(int32_t) * (size_t)cap);
+    int32_t* edge = malloc(sizeof(int32_t) * (size_t)cap);
+    int64_t off[2] = { 0, 0 };
+    int rc = SHD_ROUTE_ENOMEM;
+    if (vert && edge) {
+        pthread_mutex_lock(&t->lock);
+        rc = shd_route_paths(t->eng[0], &a, &b, 1, SHD_ROUTE_DISPATCH, off, vert, edge, cap);
+        pthread_mutex_unlock(&t->lock);
+    }
+    if (rc || off[1] < 2) {  /* (ENOEDGE: a self pair without a self-loop) */
+        free(vert); free(edge);
+        return -1;
+    }
+    *vp = vert; *ep = edge;
+    return (int32_t)(off[1] - 1);
+}
+
+int32_t shd_topology_get_path(shd_topology_t* t, int32_t s, int32_t d, int32_t* vert, int32_t* edge, int32_t cap) {
+    pcache* c;
+    int32_t i, j, *v = NULL, *e = NULL;
+    const int32_t h = route_of(t, s, d, &v, &e, &c, &i, &j);
+    if (h < 0) return -1;
+    if (vert && edge && cap >= h + 1) {
+        memcpy(vert, v, sizeof(int32_t) * ((size_t)h + 1));
+        memcpy(edge, e, sizeof(int32_t) * (size_t)h);
+    }
+    free(v); free(e);
+    return h;
+}
+
+/* the line of one route into the growable *buf; hl / hr: scratch of at least h doubles */
+static int64_t line_of(const shd_topology_t* t, const pcache* c, int32_t i, int32_t j, const int32_t* v,
+                       const int32_t* e, int32_t h, double* hl, double* hr, char** buf, size_t* cap) {
+    for (int32_t q = 0; q < h; q++) {
+        hl[q] = t->g.edge_latency[e[q]];
+        hr[q] = 1.0f - t->g.edge_packetloss[e[q]];  /* topology.c:437 */
+    }
+    return shd_topology_route_line(buf, cap, t->gml.vertex_ids, v, h + 1, hl, hr, lat_at(c, i, j), rel_at(c, i, j),
+                                   t->directed);
+}
+
+int shd_topology_format_path(shd_topology_t* t, int32_t s, int32_t d, char* buf, size_t len) {
+    pcache* c;
+    int32_t i, j, *v = NULL, *e = NULL;
+    const int32_t h = route_of(t, s, d, &v, &e, &c, &i, &j);
+    if (h < 0) return -1;
+    double* hl = malloc(sizeof(double) * 2 * ((size_t)h + 1));
+    char* line = NULL;
+    size_t lcap = 0;
+    const int64_t k = hl ? line_of(t, c, i, j, v, e, h, hl, hl + h + 1, &line, &lcap) : -1;
+    if (k >= 0 && buf && len) {
+        const size_t w = (size_t)k < len - 1 ? (size_t)k : len - 1;
+        memcpy(buf, line, w);
+        buf[w] = 0;
+    }
+    free(line); free(hl); free(v); free(e);
+    return k > 0x7FFFFFFF ? -1 : (int)k;
+}
+
+#define ROUTE_BLOCK_PAIRS (1 << 18)  /* pairs per shd_route_paths call of the dump (whole rows) */
+
+int shd_topology_dump_routes(shd_topology_t* t, FILE* out) {
+    if (!t || !out) return SHD_ROUTE_EINVAL;
+    pcache* c = cache_of(t);
+    if (!c) return SHD_ROUTE_EDEVICE;
+    int rc = SHD_ROUTE_OK;
+    int32_t *ps = NULL, *pt = NULL, *pi = NULL, *pj = NULL, *vert = NULL, *edge = NULL;
+    int64_t* off = NULL;
+    double* hl = malloc(sizeof(double) * 2 * ((size_t)t->n + 1));
+    char* line = NULL;
+    size_t lcap = 0, pcap = 0;
+    int64_t vcap = 0;
+    if (!hl) return SHD_ROUTE_ENOMEM;
+    for (int32_t i0 = 0; i0 < c->na && !rc;) {
+        /* the pairs of a block of rows that came from source paths */
+        size_t np = 0;
+        int32_t i1 = i0;
+        for (; i1 < c->na && (i1 == i0 || np + (size_t)(c->na - i1) <= ROUTE_BLOCK_PAIRS); i1++) {
+            if (np + (size_t)(c->na - i1) > pcap) {
+                pcap = 2 * (np + (size_t)(c->na - i1));
+                ps = realloc(ps, sizeof(int32_t) * pcap); pt = realloc(pt, sizeof(int32_t) * pcap);
+                pi = realloc(pi, sizeof(int32_t) * pcap); pj = realloc(pj, sizeof(int32_t) * pcap);
+                off = realloc(off, sizeof(int64_t) * (pcap + 1));
+                if (!ps || !pt || !pi || !pj || !off) { rc = SHD_ROUTE_ENOMEM; break; }
+            }
+            for (int32_t j = i1; j < c->na; j++) {
+                const int32_t a = c->A[i1], b = c->A[j];
+                if (isnan(lat_at(c, i1, j)) || pair_direct(t, a, b)) continue;
+                if (a == b && !adjacent(t, a, a)) continue;  /* the path to self (shd_route_self) */
+                ps[np] = a; pt[np] = b; pi[np] = i1; pj[np] = j;
+                np++;
+            }
+        }
+        i0 = i1;
+        if (rc || !np) continue;
+        if (vcap < (int64_t)(8 * np + 64)) {
+            vcap = (int64_t)(8 * np + 64);
+            vert = realloc(vert, sizeof(int32_t) * (size_t)vcap); edge = realloc(edge, sizeof(int32_t) * (size_t)vcap);
+            if (!vert || !edge) { rc = SHD_ROUTE_ENOMEM; break; }
+        }
+        pthread_mutex_lock(&t->lock);
+        int prc = shd_route_paths(t->eng[0], ps, pt, (int64_t)np, 0u, off, vert, edge, vcap);
+        if (prc == SHD_ROUTE_EINVAL && off[np] > vcap) {  /* longer routes than guessed: the size is in off */
+            vcap = off[np];
+            vert = realloc(vert, sizeof(int32_t) * (size_t)vcap); edge = realloc(edge, sizeof(int32_t) * (size_t)vcap);
+            prc = (vert && edge) ? shd_route_paths(t->eng[0], ps, pt, (int64_t)np, 0u, off, vert, edge, vcap)
+                                 : SHD_ROUTE_ENOMEM;
+        }
+        pthread_mutex_unlock(&t->lock);
+        if (prc && prc != SHD_ROUTE_ENOEDGE && prc != SHD_ROUTE_EUNREACH) { rc = prc; break; }
+        int64_t done = 0;  /* routes before k: each has one edge less than vertices */
+        for (size_t k = 0; k < np; k++) {
+            const int64_t nv = off[k + 1] - off[k];
+            if (nv < 2) continue;
+            const int64_t len = line_of(t, c, pi[k], pj[k], vert + off[k], edge + (off[k] - done), (int32_t)(nv - 1), hl,
+                                        hl + t->n + 1, &line, &lcap);
+            done++;
+            if (len < 0) { rc = SHD_ROUTE_ENOMEM; break; }
+            fwrite(line, 1, (size_t)len, out);
+            fputc('\n', out);
+        }
+    }
+    free(ps); free(pt); free(pi); free(pj); free(off); free(vert); free(edge); free(hl); free(line);
+    return rc;
+}
+
 int shd_topology_dump_paths(shd_topology_t* t, FILE* out) {
     if (!t || !out) return SHD_ROUTE_EINVAL;
     pcache* c = cache_of(t);

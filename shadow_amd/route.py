@@ -76,7 +76,7 @@ EXPORTS = (
     "shd_route_fill_triangle", "shd_route_host_alloc", "shd_route_host_free", "shd_route_tri_payload_async",
     "shd_route_kd_stats", "shd_route_host_alloc_lazy", "shd_route_host_wait",
     "shd_route_host_unpinned", "shd_route_plan_refresh_async", "shd_route_plan_landmarks",
-    "shd_route_plan_bind_store",
+    "shd_route_plan_bind_store", "shd_route_hops_async", "shd_route_hops", "shd_route_paths",
 )
 
 _lib = None
@@ -147,6 +147,12 @@ def load_library():
     L.shd_route_plan_bind_store.argtypes = [P, P, P, P]
     L.shd_route_kd_stats.restype = C.c_int
     L.shd_route_kd_stats.argtypes = [P, P, I32]
+    L.shd_route_hops_async.restype = C.c_int
+    L.shd_route_hops_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P]
+    L.shd_route_hops.restype = C.c_int
+    L.shd_route_hops.argtypes = [P, P, I32, P, I32, U32, P, P]
+    L.shd_route_paths.restype = C.c_int
+    L.shd_route_paths.argtypes = [P, P, P, I64, U32, P, P, P, I64]
     _lib = L
     return L
 
@@ -230,7 +236,65 @@ class RouteEngine:
         _check(load_library().shd_route_self(self._h, _p(v), len(v), _p(lat), _p(rel)), "shd_route_self")
         return lat, rel
 
+    def hops(self, sources, targets, dispatch: bool = True):
+        """shd_route_hops: (hops, row_max), the hop count of every (source, target) path
+        (int32, -1 = failed entry) and each row's maximum.  A missing self-loop or an
+        unreachable target raises RouteError; ``err.partial`` then holds the arrays."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        hops = np.empty((len(s), len(t)), np.int32); mx = np.empty(len(s), np.int32)
+        rc = load_library().shd_route_hops(self._h, _p(s), len(s), _p(t), len(t),
+                                           DISPATCH if dispatch else 0, _p(hops), _p(mx))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_hops")
+            err.partial = (hops, mx)
+            raise err
+        _check(rc, "shd_route_hops")
+        return hops, mx
+
+    def paths(self, pair_src, pair_tgt, dispatch: bool = True):
+        """shd_route_paths: (off, vert, edge) of the explicit routes of the pairs, in the
+        caller's order: vert[off[k]:off[k+1]] = pair k's vertices from source to target
+        (empty for a failed pair), its edge ids edge[eoff[k]:eoff[k] + hops] with
+        eoff = path_edge_offsets(off).  Makes the sizing call itself.  Failed pairs raise
+        RouteError with ``err.partial`` = the arrays."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        if len(s) != len(t):
+            raise ValueError("pair_src and pair_tgt differ in length")
+        L = load_library()
+        flags = DISPATCH if dispatch else 0
+        off = np.zeros(len(s) + 1, np.int64)
+        rc = L.shd_route_paths(self._h, _p(s), _p(t), len(s), flags, _p(off), None, None, 0)
+        if rc != EINVAL or off[-1] <= 0:  # EINVAL with the sizes filled in: the buffers to bring
+            if rc in (ENOEDGE, EUNREACH):
+                err = RouteError(rc, "shd_route_paths")
+                err.partial = (off, np.empty(0, np.int32), np.empty(0, np.int32))
+                raise err
+            _check(rc, "shd_route_paths")
+            return off, np.empty(0, np.int32), np.empty(0, np.int32)
+        cap = int(off[-1])
+        vert = np.full(cap, -1, np.int32); edge = np.full(cap, -1, np.int32)
+        rc = L.shd_route_paths(self._h, _p(s), _p(t), len(s), flags, _p(off), _p(vert), _p(edge), cap)
+        edge = edge[: cap - int(np.count_nonzero(np.diff(off)))]
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_paths")
+            err.partial = (off, vert, edge)
+            raise err
+        _check(rc, "shd_route_paths")
+        return off, vert, edge
+
     # -- device-pointer API (torch tensors as HBM plumbing) --------------------
+    def hops_async(self, d_src, d_tgt, d_hops, d_rowmax, stream=None, dispatch=True, ld=None):
+        """shd_route_hops_async over int32 device tensors (d_hops / d_rowmax may be None)."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_hops_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0,
+            ptr(d_hops), ptr(d_rowmax), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_hops_async")
+
     def rows_async(self, d_src, d_tgt, d_lat, d_rel, d_rowmin, stream=None, dispatch=True, ld=None):
         ns, nt = int(d_src.numel()), int(d_tgt.numel())
         ld = nt if ld is None else int(ld)
@@ -374,6 +438,14 @@ class RoutePlan:
                                                       C.c_void_p(d_prow.data_ptr()))
         _check(rc, "shd_route_plan_bind_store")
         self._store = (d_drow, d_prow)
+
+
+def path_edge_offsets(off) -> np.ndarray:
+    """Where each pair's edge ids start in shd_route_paths' edge_out, from its off_out:
+    off[k] minus the pairs before k that did not fail (each has one edge less than vertices)."""
+    off = np.asarray(off, np.int64)
+    ok = (np.diff(off) > 0).astype(np.int64)
+    return off[:-1] - (np.cumsum(ok) - ok)
 
 
 def tri16_lines(na: int, i: int | None = None) -> int:

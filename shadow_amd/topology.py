@@ -28,6 +28,7 @@ EXPORTS = (
     "shd_topology_is_direct_path", "shd_topology_min_path_latency", "shd_topology_runahead_ns",
     "shd_topology_fill", "shd_topology_dump_paths", "shd_topology_triangle_bytes",
     "shd_attach_create", "shd_attach_find_vertex", "shd_attach_destroy", "shd_topology_attach",
+    "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
 )
 
 VATTRS = ("ip", "citycode", "countrycode", "geocode", "type")  # SHD_VATTR_* order
@@ -89,6 +90,14 @@ def load_library():
     L.shd_topology_triangle_bytes.argtypes = [P]
     L.shd_topology_dump_paths.restype = C.c_int
     L.shd_topology_dump_paths.argtypes = [P, P]
+    L.shd_topology_get_path.restype = I32
+    L.shd_topology_get_path.argtypes = [P, I32, I32, P, P, I32]
+    L.shd_topology_format_path.restype = C.c_int
+    L.shd_topology_format_path.argtypes = [P, I32, I32, C.c_char_p, C.c_size_t]
+    L.shd_topology_dump_routes.restype = C.c_int
+    L.shd_topology_dump_routes.argtypes = [P, P]
+    L.shd_topology_route_line.restype = C.c_int64
+    L.shd_topology_route_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, P, I32, P, P, D, D, C.c_int]
     S = C.c_char_p
     L.shd_attach_create.restype = C.c_int
     L.shd_attach_create.argtypes = [C.POINTER(P), C.POINTER(_GraphML)]
@@ -281,6 +290,47 @@ class Topology:
 
     def runahead_ns(self) -> int:
         return int(load_library().shd_topology_runahead_ns(self._h))
+
+    def get_path(self, s, d):
+        """shd_topology_get_path: (vert, edge) of the stored Path of {s, d}, from the lower
+        attached vertex to the higher; None where the getters return -1."""
+        L = load_library()
+        cap = max(2, int(L.shd_topology_vertex_count(self._h)) + 1)
+        vert = np.empty(cap, np.int32); edge = np.empty(cap, np.int32)
+        h = L.shd_topology_get_path(self._h, int(s), int(d), C.c_void_p(vert.ctypes.data),
+                                    C.c_void_p(edge.ctypes.data), cap)
+        if h < 0:
+            return None
+        return vert[: h + 1].copy(), edge[:h].copy()
+
+    def format_path(self, s, d):
+        """shd_topology_format_path: the reference's "shortest path ..." line of the pair."""
+        L = load_library()
+        size = 4096
+        while True:
+            buf = C.create_string_buffer(size)
+            k = L.shd_topology_format_path(self._h, int(s), int(d), buf, size)
+            if k < 0:
+                return None
+            if k < size:
+                return buf.value.decode()
+            size = k + 1
+
+    def dump_routes(self, path: str):
+        """shd_topology_dump_routes into the file `path`."""
+        libc = C.CDLL(None)
+        libc.fopen.restype = C.c_void_p
+        libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+        libc.fclose.argtypes = [C.c_void_p]
+        fp = libc.fopen(str(path).encode(), b"w")
+        if not fp:
+            raise OSError(f"cannot open {path}")
+        try:
+            rc = load_library().shd_topology_dump_routes(self._h, fp)
+        finally:
+            libc.fclose(fp)
+        if rc:
+            raise RuntimeError(f"dump_routes failed ({rc})")
 
     def table(self, vertices):
         """Dense lookup(i, j) table (lat, rel) for a vertex list, via the public getters."""
