@@ -118,7 +118,9 @@ const char* shd_route_strerror(int code);
  *   row_min_out[i] = min_j lat_out[i*nt + j]   (any of the three outputs may be NULL).
  * Host pointers; the call blocks.  SHD_ROUTE_ENOEDGE / SHD_ROUTE_EUNREACH are per-entry
  * failures: every row is still written, the failed entries are NaN (the reference skips
- * storing those targets, topology.c:1812-1870) and the code is returned at the end. */
+ * storing those targets, topology.c:1812-1870) and the code is returned at the end.
+ * row_min_out[i] is the minimum over the entries of row i that did not fail, and +inf when
+ * none did. */
 int shd_route_rows(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,
                    int32_t nt, uint32_t flags, double* lat_out, double* rel_out,
                    double* row_min_out);

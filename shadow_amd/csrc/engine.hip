@@ -452,7 +452,9 @@ int prepare_k32(shd_route* c, const std::vector<int>& row, const std::vector<int
                                                       : std::min(n, std::max(1024, n / 2));
             } else qcap = (int)std::min<size_t>((size_t)n, (kLdsBudget - base - 64) / 2);
             if (const char* e = getenv("SHD_ROUTE_QCAP")) qcap = std::min(qcap, std::max(64, atoi(e)));
-            qcap &= ~7;
+            // (a multiple of 8, and never 0: with fewer than 8 vertices the rounding left an
+            // empty queue, every vertex overflowed back to pending and the bucket loop spun)
+            qcap = std::max(8, qcap & ~7);
             const size_t lds = kd_dispatch(blk, [&](auto B) { return kd_lds_bytes<decltype(B)::value>(n, qcap); });
             int maxdeg = 0;
             for (int v = 0; v < n; v++) maxdeg = std::max(maxdeg, row[v + 1] - row[v]);
@@ -545,7 +547,7 @@ int prepare_k32(shd_route* c, const std::vector<int>& row, const std::vector<int
                     // hub rows in 1024-thread workgroups: that block's queue and bucket width
                     const size_t hb = kd_lds_bytes<1024>(n, 0);
                     if (hb + 2 * 512 <= kLdsBudget) {
-                        const int hq = (int)std::min<size_t>((size_t)n, (kLdsBudget - hb - 64) / 2) & ~7;
+                        const int hq = std::max(8, (int)std::min<size_t>((size_t)n, (kLdsBudget - hb - 64) / 2) & ~7);
                         const size_t hl = kd_lds_bytes<1024>(n, hq);
                         std::vector<int> ws2(c->nnz);
                         for (int a = 0; a < c->nnz; a++) ws2[a] = (int)w[a];

@@ -214,20 +214,33 @@ class RouteEngine:
 
     # -- host-pointer API -----------------------------------------------------
     def rows(self, sources, targets, dispatch: bool = True):
+        """shd_route_rows: (lat, rel, row_min).  A per-entry failure (a missing self-loop,
+        an unreachable target) raises RouteError; ``err.partial`` then holds the arrays,
+        every row written and the failed entries NaN."""
         s = np.ascontiguousarray(sources, np.int32)
         t = np.ascontiguousarray(targets, np.int32)
         lat = np.empty((len(s), len(t))); rel = np.empty((len(s), len(t))); mn = np.empty(len(s))
         rc = load_library().shd_route_rows(self._h, _p(s), len(s), _p(t), len(t),
                                            DISPATCH if dispatch else 0, _p(lat), _p(rel), _p(mn))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_rows")
+            err.partial = (lat, rel, mn)
+            raise err
         _check(rc, "shd_route_rows")
         return lat, rel, mn
 
     def direct(self, sources, targets):
+        """shd_route_direct: (lat, rel, row_min); a pair without an edge raises RouteError
+        with ``err.partial`` = the arrays (that entry NaN), as rows()."""
         s = np.ascontiguousarray(sources, np.int32)
         t = np.ascontiguousarray(targets, np.int32)
         lat = np.empty((len(s), len(t))); rel = np.empty((len(s), len(t))); mn = np.empty(len(s))
-        _check(load_library().shd_route_direct(self._h, _p(s), len(s), _p(t), len(t), _p(lat), _p(rel), _p(mn)),
-               "shd_route_direct")
+        rc = load_library().shd_route_direct(self._h, _p(s), len(s), _p(t), len(t), _p(lat), _p(rel), _p(mn))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_direct")
+            err.partial = (lat, rel, mn)
+            raise err
+        _check(rc, "shd_route_direct")
         return lat, rel, mn
 
     def self_paths(self, vertices):
