@@ -35,6 +35,8 @@
 //
 // B  fix-ups (four vertices and four tail arcs each in flight per thread; long tails one
 //    wave per vertex), lat row out (dist is exact: integer latencies, bound < 0xFFFF).
+//    1024-thread rows run the two side by side: KD_BWAVES waves fix up (kd_fixup, wave-local,
+//    long tails eight at a time) while the others store the distance and lat rows (kd_lat_row).
 // C  reliability down the tree: parents u16 in LDS over the dead distances, relv f64 in
 //    a per-workgroup HBM slice (8n bytes do not fit LDS at this size).  Level sweeps
 //    over a pending bitmask: a vertex is ready when its parent left the pending set in
@@ -167,6 +169,11 @@ constexpr int KD_NACC = 40;
 #define KD_COUNT(slot, x) do { if (lane == 0 && (x)) atomicAdd(&sm->acc[slot], (unsigned long long)(x)); } while (0)
 #define KD_MARK() do { if (tid == 0) kd_t = __builtin_amdgcn_s_memtime(); } while (0)
 #define KD_ACC(slot) do { if (tid == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); sm->acc[slot] += t_ - kd_t; kd_t = t_; } } while (0)
+// the split region's per-wave timers (one lane of wave 0 and of the first store wave): 16 B short, 17 B
+// long | 37 distance row, 38 lat row | 39 wave 0's wait at the join
+#define KD_WDECL(on) const bool kd_st = lane == 0 && (on); unsigned long long kd_w = __builtin_amdgcn_s_memtime(); (void)kd_st; (void)kd_w
+#define KD_WMARK() do { kd_w = __builtin_amdgcn_s_memtime(); } while (0)
+#define KD_WACC(slot) do { if (kd_st) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); sm->acc[slot] += t_ - kd_w; kd_w = t_; } } while (0)
 #define KD_FLUSH() do { lds_barrier(); if (g.dbg && i >= 0) for (int q_ = tid; q_ < KD_NACC; q_ += B) g.dbg[(size_t)i * KD_NACC + q_] = sm->acc[q_]; lds_barrier(); if (tid < KD_NACC) sm->acc[tid] = 0; lds_barrier(); } while (0)
 #else
 #define KD_ACCP nullptr
@@ -177,6 +184,9 @@ constexpr int KD_NACC = 40;
 #define KD_MARK() do { } while (0)
 #define KD_ACC(slot) do { } while (0)
 #define KD_FLUSH() do { } while (0)
+#define KD_WDECL(on) do { } while (0)
+#define KD_WMARK() do { } while (0)
+#define KD_WACC(slot) do { } while (0)
 #endif
 
 // the output phases' launch-invariant arguments, staged in LDS once per launch: kd_output
@@ -229,10 +239,19 @@ struct KDSmall {
     uint32_t* wsl[2];   // the two record slices of this workgroup
     int ns;
     KDOut out;          // kd_output's launch-invariant arguments
+    // (kd_fixup's: the light in-CSR; these fill the struct's tail padding, so the LDS layout
+    // is the one it was)
+    const int* lrow;
+    const uint2* lrec;
+    int nlight, packed;
+    int latblk;         // the lat row's next block of 256 vertices (or list positions): kd_lat_row
 #ifdef SHD_STAMPS
     unsigned long long acc[KD_NACC];
 #endif
 };
+#ifndef SHD_STAMPS
+static_assert(sizeof(KDSmall) == 512, "LDS layout: KDSmall is eight 64-byte lines");
+#endif
 
 // LDS: per-wave scratch | dist u16[n+1] | pend, fix u64[nw] | wmin u32[nw] | work.
 // work holds the bucket work queue (u16 x rc) + the parent-record ring (uint2 x rr) in
@@ -294,6 +313,12 @@ constexpr int KD_MAXD = 32;           // phase C path walk: arcs held in registe
 #endif
 #ifndef KD_SEEDSPIN
 #define KD_SEEDSPIN 8  // seeded init: polls (s_sleep 8 each) of a second or third seed's flag before it is dropped (0: wait; round 4: C3 2.68 -> 2.53 ms, C4 44.7 -> 44.4)
+#endif
+#ifndef KD_BWAVES
+#define KD_BWAVES 8  // 1024-thread rows: waves that run phase B while the others store the distance and latency rows (C4, three runs each on one box: parent 40.82-41.09 ms, 2: 40.75-40.88, 4: 39.84-40.09, 8: 39.77-39.78)
+#endif
+#ifndef KD_BHELP
+#define KD_BHELP 1  // 1024-thread rows: B waves other than wave 0 take lat-row blocks once their fix-ups are done (0, at 4 B waves: 40.05-40.31 ms against 39.84-40.09)
 #endif
 #ifndef KD_WQ_N
 #define KD_WQ_N 2
@@ -486,8 +511,120 @@ __device__ inline int kd_next_source(int* ctr, int* slot, int tid, bool all_queu
     return i;
 }
 
+// a value every lane of the wave read from the same LDS word, as a wave-uniform (scalar) one
+template <class T>
+__device__ __attribute__((always_inline)) inline T kd_uni(T x) {
+    if constexpr (sizeof(T) == 8) {
+        unsigned long long b;
+        __builtin_memcpy(&b, &x, 8);
+        b = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b) |
+            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) << 32);
+        T y;
+        __builtin_memcpy(&y, &b, 8);
+        return y;
+    } else {
+        return (T)__builtin_amdgcn_readfirstlane((int)x);
+    }
+}
+
+// The latency row of one output row (i >= 0), 1024-thread rows: called in the split region
+// after phase A' by the store waves (wave KD_BWAVES and up), and by the B waves but wave 0
+// once their fix-ups are done.  No barrier in here; the row's minimum is folded into sm->rmin
+// (reset at the row's init, with the block counter).  Not inlined:
+// its registers are allocated for these loops alone, as kd_output's.
+template <int B>
+__device__ __attribute__((noinline)) void kd_lat_row(const int i, const int s, const double sw_s) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RR = kd_rr<B>();
+    KDSmall* sm = reinterpret_cast<KDSmall*>(smem);
+    const KDOut& O = sm->out;
+    const KD_GLOBAL int* __restrict__ const tgt = kd_uni(O.tgt);
+    KD_GLOBAL double* __restrict__ const lat_out = kd_uni(O.lat_out);
+    int* __restrict__ const err = kd_uni(O.err);
+    const long long ld = kd_uni(O.ld);
+    const int n = kd_uni(O.n), nt = kd_uni(O.nt), tsorted = kd_uni(O.tsorted), dflags = kd_uni(O.dflags);
+    const KDLayout<B> L = KDLayout<B>::make(n, kd_uni(O.rc), RR);
+    const int lane = (int)threadIdx.x & 63;
+    // blocks of 256 vertices (or list positions) from a counter: a wave takes the next one
+    // when it has stored its last (one LDS atomic per block, no wave waits for another)
+    auto next_block = [&]() __attribute__((always_inline)) {
+        int blk = 0;
+        if (lane == 0) blk = atomicAdd(&sm->latblk, 1);
+        return 256 * __builtin_amdgcn_readfirstlane(blk);
+    };
+    const uint16_t* dist = reinterpret_cast<const uint16_t*>(smem + L.dist);
+    const unsigned long long* tmask = reinterpret_cast<const unsigned long long*>(smem + L.tmask);
+    const unsigned* tpre = reinterpret_cast<const unsigned*>(smem + L.tpre);
+    (void)dflags;
+    KD_GLOBAL double* lrow = lat_out ? lat_out + (long long)i * ld : nullptr;
+    double lmin = INFINITY;
+    if (tsorted) {
+        // two vertex pairs per lane, 128 vertices apart, so that each of the wave's two 16-B
+        // store instructions covers 1 KB of consecutive positions: full lines (four adjacent
+        // vertices per lane, round 5's first form, split every line over two instructions and
+        // each half went to HBM on its own: C4 writes 75.6 -> 58.7 GB per launch, 41.9 -> 41.5 ms)
+        const int lpar = (int)(((uintptr_t)lrow >> 3) & 1);
+        for (int b0 = next_block(); b0 < n; b0 = next_block()) {
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const int v = b0 + 128 * p + 2 * lane;
+                if (v >= n) continue;
+                const unsigned long long wd = tmask[v >> 6];
+                const int sh = v & 63;
+                const int j = (int)tpre[v >> 6] + __popcll(wd & ((1ull << sh) - 1ull));
+                const uint32_t d2 = *reinterpret_cast<const uint32_t*>(dist + v);
+                int jq[2];
+                double Lq[2];
+                int jn = j;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int vv = v + h;
+                    const bool tg = vv < n && ((wd >> (sh + h)) & 1ull);
+                    jq[h] = tg ? jn++ : -1;
+                    const unsigned d = (d2 >> (16 * h)) & 0xFFFFu;
+                    double Lv = 0.0;
+                    if (tg) {
+                        if (vv == s) {
+                            if (isnan(sw_s)) { raise_err(err, SHD_ROUTE_ENOEDGE); Lv = NAN; }
+                            else { Lv = 0.0 + sw_s; lmin = fmin(lmin, Lv); }
+                        } else if (d == 0xFFFFu) { raise_err(err, SHD_ROUTE_EUNREACH); Lv = NAN; }
+                        else { Lv = (double)d; lmin = fmin(lmin, Lv); }
+                    }
+                    Lq[h] = Lv;
+                }
+                if (!lrow || !KD_OUT) continue;
+                const int ja = jq[0], jb = jq[1];
+                if (ja >= 0 && jb == ja + 1 && !((ja + lpar) & 1))
+                    __builtin_nontemporal_store(kd_d2{Lq[0], Lq[1]}, reinterpret_cast<KD_GLOBAL kd_d2*>(lrow + ja));
+                else {
+                    if (ja >= 0) __builtin_nontemporal_store(Lq[0], lrow + ja);
+                    if (jb >= 0) __builtin_nontemporal_store(Lq[1], lrow + jb);
+                }
+            }
+        }
+    } else {
+        for (int b0 = next_block(); b0 < nt; b0 = next_block())
+        for (int j = b0 + lane; j < min(nt, b0 + 256); j += 64) {
+            const int t = tgt[j];
+            double Lv;
+            if (t < 0 || t >= n) { raise_err(err, SHD_ROUTE_EINVAL); Lv = NAN; }
+            else if (t == s) {
+                if (isnan(sw_s)) { raise_err(err, SHD_ROUTE_ENOEDGE); Lv = NAN; }
+                else { Lv = 0.0 + sw_s; lmin = fmin(lmin, Lv); }
+            } else if (dist[t] == 0xFFFFu) { raise_err(err, SHD_ROUTE_EUNREACH); Lv = NAN; }
+            else { Lv = (double)dist[t]; lmin = fmin(lmin, Lv); }
+            if (lrow && KD_OUT) __builtin_nontemporal_store(Lv, lrow + j);
+        }
+    }
+    // the row minimum: min is exact and order-free, so row_min keeps its bits
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) lmin = fmin(lmin, __shfl_xor(lmin, d, 64));
+    if (lane == 0 && lmin < INFINITY) atomicMin(&sm->rmin, as_u(lmin));
+}
+
 // Phases C/D of one row (lat row, parent copy, reliability by walks or level sweeps, rel
-// row, row min), called once per row.  Not inlined, on purpose: see the call site.
+// row, row min), called once per row.  Not inlined, on purpose: see the call site.  1024-thread
+// rows: the lat row is written by kd_lat_row, in the split region after phase A'.
 template <int B>
 __device__ __attribute__((noinline)) void kd_output(const int i, const int s, const double cs, const double sw_s,
                                                     const double sr_s, const KD_GLOBAL uint32_t* __restrict__ wpr) {
@@ -561,6 +698,9 @@ __device__ __attribute__((noinline)) void kd_output(const int i, const int s, co
     const bool walks = g.walk && rrow;
     // (a kept row's lat row written last, from its row store, so that the parent copy's loads
     // do not queue behind the lat row's stores, measured slower: C4 41.69 against 41.30 ms)
+    // (1024-thread rows: the join of the split region did both, and the store waves wrote
+    // the lat row there: a store wave must not wait here for its 400 KB of lat stores)
+    if constexpr (B < 1024) {
     wait_stores();
     __syncthreads();
     if (tsorted) {
@@ -614,11 +754,14 @@ __device__ __attribute__((noinline)) void kd_output(const int i, const int s, co
             if (lrow && KD_OUT) __builtin_nontemporal_store(Lv, lrow + j);
         }
     }
+    }
+    (void)lrow; (void)lat_of; (void)tsorted; (void)nt; (void)tgt;
     // planned launches: the next job is taken here (queue order is unchanged: a job is still
     // taken after every job it seeds from)
     const bool queued = sm->jobs != nullptr;
     if (tid == 0) {
-        sm->deep = 0; sm->rmin = kInfBits; sm->wnext = 0; sm->wnext2 = 0; sm->novf = 0;
+        sm->deep = 0; sm->wnext = 0; sm->wnext2 = 0; sm->novf = 0;
+        if constexpr (B < 1024) sm->rmin = kInfBits;  // (1024-thread rows: at the row's init, the store waves fold into it)
         if (queued) sm->njb = atomicAdd(sm->qnext, 1);
     }
     __syncthreads();
@@ -1095,15 +1238,179 @@ __device__ __attribute__((noinline)) void kd_output(const int i, const int s, co
     }
     }  // sweep
     if (row_min && i >= 0) {
+        if constexpr (B < 1024) {
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) lmin = fmin(lmin, __shfl_xor(lmin, d, 64));
-        if (lane == 0 && lmin < INFINITY) atomicMin(&sm->rmin, as_u(lmin));
+            for (int d = 32; d >= 1; d >>= 1) lmin = fmin(lmin, __shfl_xor(lmin, d, 64));
+            if (lane == 0 && lmin < INFINITY) atomicMin(&sm->rmin, as_u(lmin));
+        }
         __syncthreads();
         if (tid == 0) row_min[i] = as_d(sm->rmin);
     }
 }
 
-#define KD_KERNEL_PARAMS                                                                                   \
+// Phase B of a 1024-thread row, wave-local: called by the first KD_BWAVES waves only, in the
+// split region after phase A' (see the call site), while the other waves store.  No workgroup
+// barrier, flag or spin in here: a wave synchronises with nothing but itself (wave_barrier).
+// Not inlined, as kd_output: phase B's registers (16 arcs in flight per lane) are allocated
+// here and not in the kernel, beside phase A's.
+template <int B>
+__device__ __attribute__((noinline)) void kd_fixup(const int s_, KD_GLOBAL uint32_t* wpr_) {
+    // (wave-uniform arguments arrive in vector registers: back to scalar ones)
+    const int s = kd_uni(s_);
+    KD_GLOBAL uint32_t* __restrict__ const wpr = kd_uni(wpr_);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RR = kd_rr<B>();
+    KDSmall* sm = reinterpret_cast<KDSmall*>(smem);
+    const int n = kd_uni(sm->out.n), nw = kd_uni(sm->out.nw);
+    const KDLayout<B> L = KDLayout<B>::make(n, kd_uni(sm->out.rc), RR);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint16_t* dist = reinterpret_cast<const uint16_t*>(smem + L.dist);
+    KD_WDECL(wid == 0);
+    {
+        // ---- B, wave-local: this wave's share of the fix words (blocks of 64 words, strided
+        // over the B waves) compacted into its slice of the work area, then four vertices x
+        // KD_TAIL speculative tail arcs per lane; long tails listed with their row bounds in
+        // its slice of qbeg and taken eight at a time, 8 lanes each
+        unsigned long long* fix = reinterpret_cast<unsigned long long*>(smem + L.fix);
+        // the light in-CSR through buffer descriptors: one offset register per vertex (its
+        // KD_TAIL arcs are immediate offsets from it) instead of a 64-bit address per load,
+        // and a load past the last arc is a range-checked no-op (its result is never used)
+        const int nlight = kd_uni(sm->nlight);
+        const __amdgpu_buffer_rsrc_t lrs =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(kd_uni(sm->lrow)), (short)0, (n + 1) * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ars =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2*>(kd_uni(sm->lrec)), (short)0, nlight * 8, 0x00020000);
+        int* __restrict__ const err = kd_uni(sm->out.err);
+        const bool packed = kd_uni(sm->packed) != 0;
+        const int qw = L.qcap / KD_BWAVES;  // (qcap >= 680: the ring alone is 8 * RR bytes)
+        uint16_t* const myq = reinterpret_cast<uint16_t*>(smem + L.qv) + wid * qw;
+        int* const myl = reinterpret_cast<int*>(smem + L.qbeg) + wid * qw;
+        // a round lists at most half a slice of vertices, so that the long tails among them
+        // ({first arc left, v | arcs left << 16}: two ints each) always fit
+        const int lcap = qw / 2;
+        const int sword = s >> 6;
+        const unsigned long long sbit = 1ull << (s & 63);
+        for (;;) {
+            int cnt = 0;  // (wave-uniform)
+            for (int k0 = 64 * wid; k0 < nw && cnt < lcap; k0 += 64 * KD_BWAVES) {
+                const int k = k0 + lane;
+                const unsigned long long had = k < nw ? fix[k] : 0ull;
+                const unsigned long long bits = k == sword ? had & ~sbit : had;  // (the source needs no parent)
+                const int c = __popcll(bits);
+                const int incl = kd_wave_incl_sum(c);
+                int pos = cnt + incl - c;
+                unsigned long long b = bits, listed = 0ull;
+                while (b && pos < lcap) {
+                    const int bi = __ffsll((long long)b) - 1;
+                    b &= b - 1;
+                    myq[pos++] = (uint16_t)((k << 6) + bi);
+                    listed |= 1ull << bi;
+                }
+                if ((bits & ~listed) != had) fix[k] = bits & ~listed;  // (had != 0: k < nw)
+                cnt = min(lcap, cnt + __builtin_amdgcn_readlane(incl, 63));
+            }
+            if (cnt == 0) break;
+            __builtin_amdgcn_wave_barrier();
+            int nlong = 0;  // (wave-uniform)
+            for (int j0 = 0; j0 < cnt; j0 += 64 * 4) {
+                int v4[4], a4[4], r4[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int j = j0 + q * 64 + lane;
+                    v4[q] = j < cnt ? (int)myq[j] : -1;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int vv = v4[q] >= 0 ? v4[q] : 0;
+                    const kd_u2 lr = __builtin_amdgcn_raw_buffer_load_b64(lrs, (uint32_t)vv << 2, 0, 0);  // lrow[vv], lrow[vv + 1]
+                    a4[q] = (int)lr.x;
+                    r4[q] = (int)lr.y;
+                }
+                kd_u2 rc[4][KD_TAIL];
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+#pragma unroll
+                    for (int e = 0; e < KD_TAIL; e++) rc[q][e] = __builtin_amdgcn_raw_buffer_load_b64(ars, (uint32_t)a4[q] << 3, 8 * e, 0);
+                unsigned dt[4][KD_TAIL], d4[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    d4[q] = ld16(dist, v4[q] >= 0 ? v4[q] : 0);
+#pragma unroll
+                    for (int e = 0; e < KD_TAIL; e++) dt[q][e] = ld16(dist, (int)(rc[q][e].x & 0xFFFFu));
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    int f = -1;
+                    uint32_t rec = KD_NONE;  // parent | ridx << 16 of the first tight arc
+#pragma unroll
+                    for (int e = KD_TAIL - 1; e >= 0; e--)
+                        if (a4[q] + e < r4[q] && dt[q][e] + (rc[q][e].x >> 16) == d4[q]) {
+                            f = e;
+                            rec = (rc[q][e].x & 0xFFFFu) | (rc[q][e].y << 16) | (packed ? (rc[q][e].x >> 16) << 24 : 0u);
+                        }
+                    const bool miss = v4[q] >= 0 && f < 0;
+                    const bool lng = miss && r4[q] - a4[q] > KD_TAIL;  // long tail: below
+                    if (miss && !lng) raise_err(err, SHD_ROUTE_EUNREACH);
+                    const unsigned long long lm = __ballot(lng);
+                    if (lng) {
+                        const int at = nlong + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(lm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)lm, 0u));
+                        // (at < cnt <= lcap; an in-row holds at most 65535 arcs: engine.hip, prepare_k32)
+                        myl[2 * at] = a4[q] + KD_TAIL;
+                        myl[2 * at + 1] = (int)((unsigned)v4[q] | ((unsigned)(r4[q] - a4[q] - KD_TAIL) << 16));
+                    } else if (v4[q] >= 0) {
+                        wpr[v4[q]] = rec;  // (every global load of this trip has been consumed)
+                    }
+                    nlong += __popcll(lm);
+                }
+            }
+            KD_WACC(16);
+            __builtin_amdgcn_wave_barrier();
+            // long tails: eight vertices per trip, 8 lanes and two blocks of 8 arcs each, every
+            // group's arcs in flight together (the row bounds come from the list: one load
+            // latency per trip, not two).  The winner is the first tight arc in arc order: the
+            // lowest tight lane of the lowest tight block (the lanes of a block hold
+            // consecutive arcs)
+            const int gi = lane >> 3, sub = lane & 7;
+            for (int j0 = 0; j0 < nlong; j0 += 8) {
+                const bool have = j0 + gi < nlong;
+                const int e0 = have ? myl[2 * (j0 + gi)] : 0;
+                const unsigned e1 = have ? (unsigned)myl[2 * (j0 + gi) + 1] : 0u;
+                const int v = (int)(e1 & 0xFFFFu);
+                int a0 = e0;
+                const int r1 = e0 + (int)(e1 >> 16);
+                const unsigned dv = ld16(dist, v);
+                uint32_t fr = KD_NONE;
+                bool open = have && a0 < r1;
+                while (__ballot(open)) {
+                    const int a = a0 + sub;
+                    const kd_u2 ra = __builtin_amdgcn_raw_buffer_load_b64(ars, (uint32_t)a << 3, 0, 0);
+                    const kd_u2 rb = __builtin_amdgcn_raw_buffer_load_b64(ars, (uint32_t)a << 3, 64, 0);
+                    const unsigned da = ld16(dist, (int)(ra.x & 0xFFFFu)), db = ld16(dist, (int)(rb.x & 0xFFFFu));
+                    const bool ta = open && a < r1 && da + (ra.x >> 16) == dv;
+                    const bool tb = open && a + 8 < r1 && db + (rb.x >> 16) == dv;
+                    const unsigned ma = (unsigned)(__ballot(ta) >> (8 * gi)) & 0xFFu;
+                    const unsigned mb = (unsigned)(__ballot(tb) >> (8 * gi)) & 0xFFu;
+                    const uint32_t ca = (ra.x & 0xFFFFu) | (ra.y << 16) | (packed ? (ra.x >> 16) << 24 : 0u);
+                    const uint32_t cb = (rb.x & 0xFFFFu) | (rb.y << 16) | (packed ? (rb.x >> 16) << 24 : 0u);
+                    const unsigned mm = ma ? ma : mb;
+                    const int from = 8 * gi + (mm ? __ffs((int)mm) - 1 : 0);
+                    const uint32_t got = (uint32_t)__shfl((int)(ma ? ca : cb), from, 64);
+                    if (open && mm) { fr = got; open = false; }
+                    if (open) { a0 += 16; open = a0 < r1; }
+                }
+                if (sub == 0 && have) {
+                    if (fr == KD_NONE) raise_err(err, SHD_ROUTE_EUNREACH);
+                    wpr[v] = fr;
+                }
+            }
+            KD_WACC(17);
+        }
+        wait_stores();  // this wave's records, before the join
+        KD_WACC(16);
+    }
+}
+
+#define KD_KERNEL_PARAMS                                                                              \
     DevDelta g, const int* __restrict__ src, int ns, const int* __restrict__ tgt, int nt, long long ld,     \
         double* __restrict__ lat_out, double* __restrict__ rel_out, double* __restrict__ row_min,          \
         int* __restrict__ err, char* __restrict__ ws, size_t ws_stride
@@ -1184,6 +1491,10 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         sm->njb = -1; sm->wpar = 0;
         sm->jobs = g.jobs; sm->qnext = g.next; sm->drow = g.drow; sm->prow = g.prow; sm->rstride = g.rstride;
         sm->done = g.done; sm->ns = ns;
+        if constexpr (B >= 1024) {
+            sm->lrow = g.lrow; sm->lrec = g.lrec;
+            sm->nlight = g.nlight; sm->packed = g.packed;
+        }
         sm->wsl[0] = wslice;
         sm->wsl[1] = reinterpret_cast<uint32_t*>(ws + (size_t)blockIdx.x * ws_stride + kd_ws_wpr1(n));
         KDOut& o = sm->out;
@@ -1353,6 +1664,10 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
             sm->gmin[0] = sm->gmin[1] = 0xFFFFFFFFu;
             sm->rtail = sm->rdone = 0;
             sm->nev = 0; sm->evovf = 0;
+            if constexpr (B >= 1024) {  // the split region's: the lat row's minimum (the previous row's
+                sm->rmin = kInfBits;    // was written out before the barrier that ended it) and block counter
+                sm->latblk = 0;
+            }
             wpr_of()[s] = KD_SRC_MARK;
         }
         lds_barrier();
@@ -1859,6 +2174,56 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         // re-queued (qbeg) for one wave per vertex
         const int last_arc = g.nlight > 0 ? g.nlight - 1 : 0;
         uint32_t* const wpr = wpr_of();  // (phases B and C)
+        if constexpr (B >= 1024) {
+        // ---- split region (1024-thread rows): phase B | distance row + lat row ------------
+        // The distances are final.  The first KD_BWAVES waves fix up parents (kd_fixup): they
+        // read dist, own fix and the work area, and write wpr.  The other waves (store waves)
+        // read dist, tmask and tpre and write the row-store slot and the lat row.  Neither
+        // side writes what the other reads, and inside the region a wave synchronises with
+        // nothing but itself: no s_barrier, no flag, no spin.  Both sides meet at one
+        // lds_barrier, which does not wait for stores.
+        // The ready flag: a seeded row reads this row's dist slot and its parent records
+        // (wpr: the init's, the writer wave's and A's, all waited for by every wave before
+        // A' ended; and phase B's).  Each B wave waits vmcnt(0) on its record stores at the
+        // end of kd_fixup, before the join and before any lat block it then takes, and each
+        // store wave waits vmcnt(0) on its distance-row stores before its first lat store, so
+        // at the join every such byte has left this CU for L2.  Thread 0 (wave 0: it takes no
+        // lat blocks, so it has no lat stores to wait for) then does the agent-scope release
+        // and raises the flag, as before.  The lat-row stores may still be in flight: no row
+        // reads them.
+        static_assert(KD_BWAVES >= 1 && KD_BWAVES < NW, "B waves and store waves");
+        constexpr int NSW = NW - KD_BWAVES;
+        const int store = __builtin_amdgcn_readfirstlane(sm->job.store);
+        KD_WDECL(wid == 0 || wid == KD_BWAVES);
+        if (wid < KD_BWAVES) {
+            kd_fixup<B>(s, (KD_GLOBAL uint32_t*)wpr);
+            KD_WMARK();  // (wave 0 stamped its own time inside)
+            // fix-ups done (records waited for): help with what is left of the lat row.  Not
+            // wave 0: thread 0 waits vmcnt(0) for the flag, and must have no lat stores then
+            if (KD_BHELP && wid > 0 && i >= 0) kd_lat_row<B>(i, s, sw_s);
+        } else {
+            // the distance row of a kept row (this row seeds later ones: u16, incl. the pad),
+            // waited for before anything else is stored; then the lat row
+            // (streaming stores for the distance row measured the same: C4 41.87 / 41.91
+            // against 41.93 / 41.89 ms)
+            if (store >= 0) {
+                uint16_t* dr = g.drow_out + (size_t)store * g.rstride;
+                for (int v0 = 8 * (tid - 64 * KD_BWAVES); v0 <= n; v0 += 8 * 64 * NSW)
+                    *reinterpret_cast<uint4*>(dr + v0) = *reinterpret_cast<const uint4*>(dist + v0);
+                wait_stores();
+            }
+            KD_WACC(37);
+            if (i >= 0) kd_lat_row<B>(i, s, sw_s);  // (helper rows have none)
+            KD_WACC(38);
+        }
+        lds_barrier();  // the join
+        if (wid == 0) KD_WACC(39);
+        if (store >= 0 && tid == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(&g.done[store], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        } else {
         if (tid == 0) {
             fix[s >> 6] &= ~(1ull << (s & 63));
             sm->qtail[0] = sm->qtail[1] = 0;
@@ -1978,6 +2343,7 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __hip_atomic_store(&g.done[store], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+        }
         }
         KD_STAMP(2);
         // output phases in their own function: its registers are allocated for these loops

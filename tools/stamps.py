@@ -110,6 +110,13 @@ if eng.info["kernel"] == 4:
     for k, nm in [(11, "minreduce"), (8, "gather"), (9, "prep"), (10, "expand"), (16, "B.short"), (17, "B.long"),
                   (18, "lat row+drain"), (19, "par copy"), (13, "C.compute")]:
         print(f"  A.{nm:10s} mean {d[:, k].mean():10.0f} cyc  ({d[:, k].mean() / max(d[:, 5].mean(), 1):.0f}/sweep)")
+    if eng.info["block"] >= 1024:
+        # the split region after A' (sssp_delta.hpp): B.short / B.long above are wave 0's own passes
+        # (B.short with its list scans and the wait for its record stores); these are the first
+        # store wave's two parts and wave 0's wait at the join (0 when the store waves arrive first)
+        print(f"  split region: wave 0 B {d[:, 16].mean() + d[:, 17].mean():.0f} (p50 {np.median(d[:, 16] + d[:, 17]):.0f})  |  store wave: "
+              f"distance row {d[:, 37].mean():.0f}  lat row {d[:, 38].mean():.0f}  |  wave 0 waits at the join {d[:, 39].mean():.0f} "
+              f"(p50 {np.median(d[:, 39]):.0f}) cyc/row")
     print(f"  pre-init: walk (wave 0) {d[:, 32].mean():.0f}  barrier wait {d[:, 33].mean():.0f}  pre-init wave {d[:, 34].mean():.0f} cyc/row; "
           f"rows started pre-initialised {d[:, 35].sum():.0f} of {len(d)}")
     t0 = d[:, 0] - d[:, 0].min()
