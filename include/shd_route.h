@@ -354,6 +354,15 @@ void shd_route_host_free(void* p);
  * hundreds.  Synchronises the device; reset != 0 zeroes the counters. */
 int shd_route_kd_stats(shd_route_t* ctx, uint64_t* out, int32_t reset);
 
+/* A seeded plan's job records, in queue order (diagnostics; no reference equivalent): the
+ * launch's job array as the rows kernel reads it, 64 bytes per job -- int32 row, s, store,
+ * nseed, seed[3], u[3], wr[3], rec[3] (only the first nseed entries of each array mean
+ * anything).  *njobs is always set; out == NULL only asks for it, a buffer of fewer than
+ * 64 * *njobs bytes is SHD_ROUTE_EINVAL, an unseeded plan SHD_ROUTE_EUNSUPPORTED.
+ * Synchronises the device (a device-built plan's records are those of its last refresh). */
+int shd_route_plan_jobs(shd_route_t* ctx, const shd_route_plan_t* plan, int32_t* njobs, void* out,
+                        int64_t out_bytes);
+
 /* K4: all-pairs shortest latencies by blocked min-plus
  * Floyd-Warshall over all vertices, u16 on the device (kept in the context).  Integer
  * latencies with every shortest path below 65535 ms, n <= 12000, simple graphs; else

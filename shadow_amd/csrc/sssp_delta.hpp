@@ -67,7 +67,7 @@ constexpr int KD_IMP = 192;  // per-wave list of improving arcs (v | nd << 16), 
 constexpr uint32_t KD_NONE = 0xFFFFFFFFu;      // no parent recorded
 constexpr uint32_t KD_SRC_MARK = 0xFFFFFFFEu;  // parent record of the source itself
 
-// Seeded rows (planned launches, engine.hip shd_route_plan_*).  A source s whose
+// Seeded rows (planned launches, plan.hpp shd_route_plan_*).  A source s whose
 // neighbour u already has its row (dist d_u and parent records p_u, kept in a row
 // store) starts from D0(v) = w(s,u) + d_u(v) instead of infinity.  D0 is a set of
 // path lengths that is already consistent (d_u(x) <= d_u(v) + w(v,x) for every arc),
@@ -86,7 +86,7 @@ constexpr uint32_t KD_SRC_MARK = 0xFFFFFFFEu;  // parent record of the source it
 #define KD_GLOBAL __attribute__((address_space(1)))
 
 #ifndef KD_NSEEDS
-#define KD_NSEEDS 3  // seeds per row at most (KDJob holds up to 3; the planner's default: engine.hip)
+#define KD_NSEEDS 3  // seeds per row at most (KDJob holds up to 3; the planner's default: plan.hpp)
 #endif
 constexpr int KD_SEEDS = KD_NSEEDS;
 #ifndef KD_NTLOAD

@@ -57,6 +57,12 @@ class _Info(C.Structure):
     ]
 
 
+# one KDJob (sssp_delta.hpp): a 64-byte record of the planned launch's job array
+JOB_DTYPE = np.dtype([("row", "<i4"), ("s", "<i4"), ("store", "<i4"), ("nseed", "<i4"), ("seed", "<i4", 3),
+                      ("u", "<i4", 3), ("wr", "<i4", 3), ("rec", "<i4", 3)])
+assert JOB_DTYPE.itemsize == 64
+
+
 class _PlanInfo(C.Structure):
     _fields_ = [
         ("rows", C.c_int32), ("seeded", C.c_int32), ("launches", C.c_int32), ("levels", C.c_int32),
@@ -77,6 +83,7 @@ EXPORTS = (
     "shd_route_kd_stats", "shd_route_host_alloc_lazy", "shd_route_host_wait",
     "shd_route_host_unpinned", "shd_route_plan_refresh_async", "shd_route_plan_landmarks",
     "shd_route_plan_bind_store", "shd_route_hops_async", "shd_route_hops", "shd_route_paths",
+    "shd_route_plan_jobs",
 )
 
 _lib = None
@@ -145,6 +152,8 @@ def load_library():
                                            C.POINTER(C.c_int64)]
     L.shd_route_plan_bind_store.restype = C.c_int
     L.shd_route_plan_bind_store.argtypes = [P, P, P, P]
+    L.shd_route_plan_jobs.restype = C.c_int
+    L.shd_route_plan_jobs.argtypes = [P, P, C.POINTER(C.c_int32), P, I64]
     L.shd_route_kd_stats.restype = C.c_int
     L.shd_route_kd_stats.argtypes = [P, P, I32]
     L.shd_route_hops_async.restype = C.c_int
@@ -443,6 +452,20 @@ class RoutePlan:
             return None
         _check(rc, "shd_route_plan_landmarks")
         return {"nland": a.value, "first": b.value, "count": c.value, "row_stride": d.value}
+
+    def jobs(self):
+        """shd_route_plan_jobs: the job records of a seeded plan in queue order, as a structured
+        array (JOB_DTYPE: row, s, store, nseed, seed[3], u[3], wr[3], rec[3]); None for an
+        unseeded plan.  Synchronises the device."""
+        L = load_library()
+        nj = C.c_int32()
+        rc = L.shd_route_plan_jobs(self.eng._h, self._h, C.byref(nj), None, 0)
+        if rc == EUNSUPPORTED:
+            return None
+        _check(rc, "shd_route_plan_jobs")
+        out = np.zeros(nj.value, JOB_DTYPE)
+        _check(L.shd_route_plan_jobs(self.eng._h, self._h, C.byref(nj), _p(out), out.nbytes), "shd_route_plan_jobs")
+        return out
 
     def bind_store(self, d_drow, d_prow):
         """Move the landmark store into caller tensors (int16 / int32, nland x row_stride at

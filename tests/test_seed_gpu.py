@@ -107,25 +107,30 @@ def test_plans_independent_of_host_workers(oracle_mod, kd):
     g = _graph("c2")
     T = g.targets()
     eng = route.RouteEngine(g)
-    ref = eng.plan(T).info
+
+    def build(e):  # the plan's shape and its whole job array, in queue order
+        p = e.plan(T)
+        return p.info, p.jobs().tobytes()
+
+    ref, ref_jobs = build(eng)
     assert ref["seeded"] == 1
     kd.setenv("SHD_ROUTE_GPUCHOICE", "0")  # seed choices on the host workers, not the device
-    assert eng.plan(T).info == ref
+    assert build(eng) == (ref, ref_jobs)
     kd.setenv("SHD_ROUTE_PIPE", "0")
-    assert eng.plan(T).info == ref
+    assert build(eng) == (ref, ref_jobs)
     kd.delenv("SHD_ROUTE_PIPE")
     engs = [route.RouteEngine(g) for _ in range(2)]
     out = [None, None]
 
     def run(i):
-        out[i] = engs[i].plan(T).info
+        out[i] = build(engs[i])
 
     th = [threading.Thread(target=run, args=(i,)) for i in range(2)]
     for t in th:
         t.start()
     for t in th:
         t.join(timeout=120)
-    assert out[0] == ref and out[1] == ref
+    assert out[0] == (ref, ref_jobs) and out[1] == (ref, ref_jobs)
     lat, rel, _ = engs[1].rows(T[::5], T, dispatch=False)
     olat, orel, _, _ = oracle_mod.OracleGraph(g).source_rows(T[::5], T, oracle_mod.TIE_MINKEY)
     assert np.array_equal(lat, olat) and np.array_equal(rel, orel)
@@ -154,6 +159,31 @@ def test_partition_forest_device_equals_host(kd, cfg, world):
         assert shape(p.info) == shape(dev[r][0])
         assert np.array_equal(p.positions, dev[r][1])
         p.close()
+
+
+def _recorded_plans():
+    with open(os.path.join(GOLD, "plan_jobs.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("case", sorted(_recorded_plans()))
+def test_plan_jobs_match_recorded(monkeypatch, case):
+    """The planner's output itself, not only the rows it leads to (which are bit-exact under
+    any plan): each recorded case's plan info, positions and job array in queue order
+    (seed choices, offsets, records, store slots) against tests/golden/plan_jobs.json, which
+    was recorded once from the planner as it stood when shd_route_plan_jobs was added
+    (tests/golden/make_plan_jobs.py).  A mismatch is a change of planner behaviour."""
+    from tests.golden import make_plan_jobs as mk
+    for k in [k for k in os.environ if k.startswith("SHD_ROUTE_")]:
+        monkeypatch.delenv(k)
+    for k, v in mk.case_env(case).items():
+        monkeypatch.setenv(k, v)
+    got, want = mk.record(case), _recorded_plans()[case]
+    assert got["info"] == want["info"]
+    assert got["positions"] == want["positions"]
+    assert got["njobs"] == want["njobs"] and got["jobs"] == want["jobs"]
+    if case == "dir-fallback":
+        assert got["info"]["seeded"] == 0 and got["jobs"] is None  # (the accessor: EUNSUPPORTED)
 
 
 def test_directed_plan_falls_back(oracle_mod, kd):

@@ -5,7 +5,7 @@ import numpy as np, torch
 torch.cuda.init()
 from shadow_amd.route import RouteEngine
 from shadow_amd.graph import config
-g = config("c4")
+g = config(sys.argv[1] if len(sys.argv) > 1 else "c4")  # (c3: the device-built landmark-only plans)
 eng = RouteEngine(g)
 T = np.sort(g.targets()).astype(np.int32)
 for W, r in [(1, 0), (8, 0), (8, 3), (2, 1)]:
