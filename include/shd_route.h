@@ -11,7 +11,8 @@
  * and shd_route_rows_planned_async share the context's work-queue counter and
  * per-workgroup scratch, so two of them must not be in flight together (enqueue them
  * on one stream, or synchronise in between).  The path hops calls (shd_route_hops*,
- * shd_route_paths) run a rows launch inside and fall under the same rule.
+ * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
+ * rows launch inside and fall under the same rule.
  *
  * Reference interface each entry point replaces (file:line in the reference):
  *   shd_route_create   <- _topology_loadGraph/_topology_checkGraph/_topology_extractEdgeWeights
@@ -29,6 +30,8 @@
  *   shd_route_self     <- _topology_computeShortestPathToSelf (topology.c:1545-1653)
  *   shd_route_min_reduce <- minimumPathLatency tracking (topology.c:1374-1385)
  *   shd_route_fw       <- (no reference equivalent; dense all-pairs alternative)
+ *   shd_route_loads, shd_route_pair_loads <- (no reference equivalent; per-link and
+ *                         per-router traffic of the chosen paths)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -182,6 +185,50 @@ int shd_route_hops(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32
  * cap 0: the sizing call).  A vertex out of range is SHD_ROUTE_EINVAL for the whole call. */
 int shd_route_paths(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs,
                     uint32_t flags, int64_t* off_out, int32_t* vert_out, int32_t* edge_out, int64_t cap);
+
+/* ---- link loads: per-edge and per-vertex weight of the chosen paths ----------------------
+ * No reference equivalent (Shadow 1.14 counts packets per cached Path only, path.c:57-60).
+ * Entries are those of shd_route_hops*, same flags; the load of an entry (s, t) with weight
+ * w goes where shd_route_paths puts that entry's route:
+ *   t != s : w is added to edge_load[e] of every edge id e on the chosen path (the tie rule
+ *            above; on a multigraph the lowest tight edge id of each hop, the edge
+ *            shd_route_paths reports) and to transit[v] of every intermediate vertex v of the
+ *            path, not of s or t.
+ *   t == s : w goes on the lowest self-loop edge of s, no transit; without a self-loop the
+ *            entry fails with SHD_ROUTE_ENOEDGE.
+ *   unreachable t : the entry fails with SHD_ROUTE_EUNREACH.
+ * With SHD_ROUTE_DISPATCH a complete graph, or prefer-direct with an adjacent pair, puts w on
+ * the direct edge (the lowest edge id joining the pair), no transit.  A failed entry never
+ * stops the rest; it fails whatever its weight, and its weight is added to *unrouted.  The
+ * code comes back at the end (shd_route_loads, shd_route_pair_loads) or by the next
+ * shd_route_sync (shd_route_loads_async).  Repeated targets and repeated pairs add up.  On an
+ * undirected graph an edge has one load for both directions.  All sums are u64 integer adds:
+ * exact (modulo 2^64) and independent of order.
+ * The sums go down each source's shortest-path tree, O(n) per source: the hop depth of every
+ * vertex orders the tree into levels, and from the deepest level up every vertex hands its
+ * subtree's sum to its parent.  The calls run a rows launch inside (the "one rows launch at a
+ * time" rule covers them) and follow the hops calls' scratch: per source of a chunk an f64
+ * distance row, a u32 parent row and an i32 hop row over all vertices, chunks sized to
+ * SHD_ROUTE_HOPS_SCRATCH (1 GiB).  The per-source sums live in LDS (22 bytes per vertex) or,
+ * on larger graphs and with SHD_ROUTE_LOADS_LDS=0, in HBM slices of 16 to 512 workgroup slots
+ * within a quarter of that budget.  Diagnostic rate: every call runs the sources' SSSP. */
+#define SHD_ROUTE_LOADS_ADD 0x400u /* add into the outputs instead of zeroing them first */
+/* Device pointers, as shd_route_hops_async: d_wt[i*ld + j] = the weight of (src[i], tgt[j]),
+ * NULL = 1 per entry (how many of the listed pairs route over each link);
+ * d_edge_load[n_edges], d_transit[n_vertices], d_unrouted[1]; any output may be NULL. */
+int shd_route_loads_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                          int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                          uint64_t* d_edge_load, uint64_t* d_transit, uint64_t* d_unrouted, void* stream);
+/* Same with host pointers (row stride nt); blocks.  A vertex out of range is SHD_ROUTE_EINVAL
+ * for the whole call, nothing written. */
+int shd_route_loads(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                    uint32_t flags, const uint64_t* wt, uint64_t* edge_load_out, uint64_t* transit_out,
+                    uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[k], pair_tgt[k], pair_wt[k]) in any order (pair_wt NULL =
+ * 1 each), grouped by source inside as shd_route_paths groups them.  Host pointers; blocks. */
+int shd_route_pair_loads(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                         const uint64_t* pair_wt, int64_t npairs, uint32_t flags, uint64_t* edge_load_out,
+                         uint64_t* transit_out, uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

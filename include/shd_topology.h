@@ -56,6 +56,7 @@ shd_topology_t* shd_topology_new_from_graph(const shd_graph_t* g, const int* dev
 void shd_topology_free(shd_topology_t* top);  /* topology_free (topology.c:2441) */
 
 int32_t shd_topology_vertex_count(const shd_topology_t* top);
+int32_t shd_topology_edge_count(const shd_topology_t* top);  /* edge ids are 0 .. count - 1, document order */
 int32_t shd_topology_find_vertex(const shd_topology_t* top, const char* graphml_id);
 
 /* topology_attach's effect on routing (topology.c:2371-2439): the vertex joins
@@ -94,6 +95,9 @@ double shd_topology_get_latency(shd_topology_t* top, int32_t src, int32_t dst);
 double shd_topology_get_reliability(shd_topology_t* top, int32_t src, int32_t dst);
 int shd_topology_is_routable(shd_topology_t* top, int32_t src, int32_t dst);
 void shd_topology_increment_path_packet_counter(shd_topology_t* top, int32_t src, int32_t dst);
+/* many packets of one pair at once: the same counter (its u32 word and the spill past 2^32) as
+ * that many increments (no reference equivalent) */
+void shd_topology_add_path_packets(shd_topology_t* top, int32_t src, int32_t dst, uint64_t packets);
 uint64_t shd_topology_get_path_packet_count(shd_topology_t* top, int32_t src, int32_t dst);
 int shd_topology_is_direct_path(shd_topology_t* top, int32_t src, int32_t dst);
 
@@ -147,6 +151,34 @@ int shd_topology_dump_routes(shd_topology_t* top, FILE* out);
 int64_t shd_topology_route_line(char** buf, size_t* cap, char* const* names, const int32_t* vert, int32_t nv,
                                 const double* hop_lat, const double* hop_rel, double lat, double rel,
                                 int directed);
+
+/* ---- link loads: the traffic of every link and every router ------------------------------
+ * No reference equivalent: Shadow 1.14 counts packets per cached Path (path.c:57-60,
+ * shd_topology_dump_paths), not per link.  These calls put every cached pair's packet count
+ * on the route of its stored Path (shd_route_pair_loads in shd_route.h).  Like the route
+ * calls above they run on engine 0 under the topology lock, compute on demand, cache nothing
+ * and change no accessor. */
+
+/* Per-link and per-router packet totals of the cached Paths' counters: every cached pair with
+ * a non-zero packet count, in its stored orientation (lower attached vertex -> higher), with
+ * the dispatch the cache used.  edge_packets[n_edges] = packets over each edge id,
+ * transit_packets[n_vertices] = packets through each vertex as an intermediate hop,
+ * *unrouted = packets of self pairs stored as the path to self (no self-loop), which is not
+ * a route of the graph's edges; each may be NULL.  Counts past 2^32 stay exact.  Before the
+ * first fill every total is zero. */
+int shd_topology_link_loads(shd_topology_t* top, uint64_t* edge_packets, uint64_t* transit_packets,
+                            uint64_t* unrouted);
+/* One line per edge with a non-zero total, in edge-id order:
+ *   link A<-->B (i<-->j) edge E is L ms with P loss, N packets
+ * ("-->" on directed graphs; A, B = the edge's ends as the graph lists them, named as in the
+ * route line). */
+int shd_topology_dump_link_loads(shd_topology_t* top, FILE* out);
+/* The formatter alone, a pure host function (link_fmt.c): edge id, its ends a and b, its
+ * latency (ms) and packet loss, the packet total; names and the growable *buf / *cap as
+ * shd_topology_route_line.  Returns the length without the NUL, -1 on a bad argument or
+ * allocation failure. */
+int64_t shd_topology_link_line(char** buf, size_t* cap, char* const* names, int32_t edge, int32_t a, int32_t b,
+                               double latency, double loss, uint64_t packets, int directed);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@
 #include "direct_fw.hpp"
 #include "fw.hpp"
 #include "path_hops.hpp"
+#include "link_loads.hpp"
 
 using namespace shd;
 
@@ -184,6 +185,9 @@ struct shd_route {
     int* d_hp_self = nullptr; int* d_hp_ident = nullptr; int* d_hp_saved = nullptr;
     char* d_hp_ws = nullptr; size_t hp_ws_stride = 0;
     char* d_hp_buf = nullptr; size_t hp_buf_cap = 0;
+    // link loads (link_loads.hpp): the workgroup slices of the tree sums' HBM form
+    int ld_ready = 0;
+    char* d_ld_ws = nullptr; size_t ld_ws_cap = 0;
     uint64_t device_bytes = 0;
     // host copies needed for lazy dense build
     std::vector<int32_t> e_src, e_dst;
@@ -1007,6 +1011,7 @@ void shd_route_destroy(shd_route_t* c) {
     if (c->d_hub_ws) (void)hipFree(c->d_hub_ws);
     if (c->d_hp_ws) (void)hipFree(c->d_hp_ws);
     if (c->d_hp_buf) (void)hipFree(c->d_hp_buf);
+    if (c->d_ld_ws) (void)hipFree(c->d_ld_ws);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
 }
@@ -2262,6 +2267,261 @@ int shd_route_paths(shd_route_t* c, const int32_t* pair_src, const int32_t* pair
         std::memcpy(edge_out + (off_out[k] - done), se.data() + geo[gq], sizeof(int32_t) * (size_t)h);
         done++;
     }
+    return soft;
+}
+
+}  // extern "C"
+
+// =============================================================================
+// Link loads (link_loads.hpp): per-edge and per-vertex weight of the chosen paths
+// =============================================================================
+namespace {
+
+// the tree sums of k sources (loads_tree_kernel), state in LDS or in HBM slices
+int ld_tree(shd_route* c, const uint32_t* par, const int32_t* hrow, const int32_t* d_src, int k,
+            const int32_t* d_tgt, int nt, long long ld, const long long* d_eoff, const uint64_t* d_wt, int mode,
+            uint64_t* d_edge, uint64_t* d_transit, uint64_t* d_unrouted, hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    auto* wt = (const unsigned long long*)d_wt;
+    auto* el = (unsigned long long*)d_edge;
+    auto* tr = (unsigned long long*)d_transit;
+    auto* un = (unsigned long long*)d_unrouted;
+    if (mode == 2) {  // no tree, no state
+        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, false, 1024>), dim3(std::min(k, 1024)), dim3(1024), kLdSmall,
+                           st, g, par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, (char*)nullptr,
+                           (size_t)0, c->d_err);
+        return hip_check(hipGetLastError());
+    }
+    const size_t lds_bytes = kLdSmall + ld_state_bytes<uint16_t>(n);
+    const bool fits = n <= 65535 && lds_bytes <= kLdsBudget;
+    if (fits && !c->ld_ready) {
+        int rc = hip_check(hipFuncSetAttribute((const void*)loads_tree_kernel<uint16_t, true, 1024>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+        if (rc) return rc;
+        c->ld_ready = 1;
+    }
+    const char* e = getenv("SHD_ROUTE_LOADS_LDS");  // "0": the HBM form on graphs the LDS form takes
+    if (fits && !(e && *e && atoi(e) == 0)) {
+        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, true, 1024>), dim3(std::min(k, 1024)), dim3(1024), lds_bytes,
+                           st, g, par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, (char*)nullptr,
+                           (size_t)0, c->d_err);
+        return hip_check(hipGetLastError());
+    }
+    // HBM slices: a quarter of the hops scratch budget, 16 to 512 workgroup slots
+    const bool small = n <= 65535;
+    const size_t stride = a16(small ? ld_state_bytes<uint16_t>(n) : ld_state_bytes<uint32_t>(n));
+    const int slots = (int)std::max<size_t>(16, std::min<size_t>(512, hp_budget() / 4 / stride));
+    const int grid = std::min(k, slots);
+    if (stride * (size_t)grid > c->ld_ws_cap) {
+        // a launch of this context that still uses the old slices is on the same stream or
+        // synchronised (one rows launch at a time): wait before the slices go
+        if (c->d_ld_ws) {
+            if (hipStreamSynchronize(st) != hipSuccess) return SHD_ROUTE_EDEVICE;
+            (void)hipFree(c->d_ld_ws);
+        }
+        c->d_ld_ws = nullptr;
+        c->ld_ws_cap = 0;
+        if (hipMalloc((void**)&c->d_ld_ws, stride * (size_t)slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
+        c->ld_ws_cap = stride * (size_t)slots;
+    }
+    if (small)
+        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, false, 1024>), dim3(grid), dim3(1024), kLdSmall, st, g, par,
+                           hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, c->d_ld_ws, stride, c->d_err);
+    else
+        hipLaunchKernelGGL((loads_tree_kernel<uint32_t, false, 1024>), dim3(grid), dim3(1024), kLdSmall, st, g, par,
+                           hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, c->d_ld_ws, stride, c->d_err);
+    return hip_check(hipGetLastError());
+}
+
+// The loads of ns sources added into the outputs, sources in chunks of the hops scratch:
+// per source a distance row, a parent row and a hop row over all vertices.  Entries: the
+// block (d_eoff null: d_tgt[nt], d_wt row stride ld) or the sparse lists d_eoff gives.
+int ld_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
+               const long long* d_eoff, const uint64_t* d_wt, uint32_t flags, uint64_t* d_edge, uint64_t* d_transit,
+               uint64_t* d_unrouted, hipStream_t st) {
+    int rc = ensure_hops(c);
+    if (rc) return rc;
+    const int n = c->n;
+    const int mode = hp_mode(c, flags);
+    if (mode == 2)
+        return ld_tree(c, nullptr, nullptr, d_src, ns, d_tgt, nt, ld, d_eoff, d_wt, 2, d_edge, d_transit, d_unrouted, st);
+    const size_t per = (size_t)n * (sizeof(double) + sizeof(uint32_t) + sizeof(int32_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)ns, hp_budget() / per));
+    if ((rc = hp_scratch(c, per * (size_t)chunk))) return rc;
+    double* dist = (double*)c->d_hp_buf;
+    uint32_t* par = (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)n * (size_t)chunk);
+    int32_t* hrow = (int32_t*)(c->d_hp_buf + (sizeof(double) + sizeof(uint32_t)) * (size_t)n * (size_t)chunk);
+    for (int i0 = 0; i0 < ns; i0 += chunk) {
+        const int k = std::min(chunk, ns - i0);
+        if ((rc = hp_rows(c, d_src + i0, k, dist, par, st))) return rc;
+        if ((rc = hp_depth(c, par, d_src + i0, k, c->d_hp_ident, n, (long long)n, 0, 1, hrow, nullptr, st))) return rc;
+        if ((rc = ld_tree(c, par, hrow, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr,
+                          d_wt && !d_eoff ? d_wt + (long long)i0 * ld : d_wt, mode, d_edge, d_transit, d_unrouted, st)))
+            return rc;
+    }
+    return SHD_ROUTE_OK;
+}
+
+// zero the outputs a call without SHD_ROUTE_LOADS_ADD starts from
+int ld_zero(shd_route* c, uint32_t flags, uint64_t* d_edge, uint64_t* d_transit, uint64_t* d_unrouted, hipStream_t st) {
+    if (flags & SHD_ROUTE_LOADS_ADD) return SHD_ROUTE_OK;
+    if ((d_edge && c->m && hipMemsetAsync(d_edge, 0, sizeof(uint64_t) * (size_t)c->m, st) != hipSuccess) ||
+        (d_transit && hipMemsetAsync(d_transit, 0, sizeof(uint64_t) * (size_t)c->n, st) != hipSuccess) ||
+        (d_unrouted && hipMemsetAsync(d_unrouted, 0, sizeof(uint64_t), st) != hipSuccess))
+        return SHD_ROUTE_EDEVICE;
+    return SHD_ROUTE_OK;
+}
+
+// device accumulators of the blocking calls: zeroed, summed into by every chunk, then copied
+// (or, with SHD_ROUTE_LOADS_ADD, added) into the caller's host arrays
+struct LoadsOut {
+    DevBuf de, dt, du;
+    int m = 0, n = 0;
+    int init(const shd_route* c) {
+        m = c->m; n = c->n;
+        int rc;
+        if ((rc = de.alloc(sizeof(uint64_t) * (size_t)m)) || (rc = dt.alloc(sizeof(uint64_t) * (size_t)n)) ||
+            (rc = du.alloc(sizeof(uint64_t))))
+            return rc;
+        if ((m && hipMemset(de.p, 0, sizeof(uint64_t) * (size_t)m) != hipSuccess) ||
+            hipMemset(dt.p, 0, sizeof(uint64_t) * (size_t)n) != hipSuccess ||
+            hipMemset(du.p, 0, sizeof(uint64_t)) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        return SHD_ROUTE_OK;
+    }
+    static int take(uint64_t* out, const void* dev, size_t count, bool add) {
+        if (!out || !count) return SHD_ROUTE_OK;
+        if (!add) return hipMemcpy(out, dev, sizeof(uint64_t) * count, hipMemcpyDeviceToHost) == hipSuccess
+                             ? SHD_ROUTE_OK : SHD_ROUTE_EDEVICE;
+        std::vector<uint64_t> h(count);
+        if (hipMemcpy(h.data(), dev, sizeof(uint64_t) * count, hipMemcpyDeviceToHost) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        for (size_t q = 0; q < count; q++) out[q] += h[q];
+        return SHD_ROUTE_OK;
+    }
+    int finish(uint32_t flags, uint64_t* edge_out, uint64_t* transit_out, uint64_t* unrouted_out) {
+        const bool add = (flags & SHD_ROUTE_LOADS_ADD) != 0;
+        int rc;
+        if ((rc = take(edge_out, de.p, (size_t)m, add)) || (rc = take(transit_out, dt.p, (size_t)n, add)) ||
+            (rc = take(unrouted_out, du.p, 1, add)))
+            return rc;
+        return SHD_ROUTE_OK;
+    }
+};
+
+// the outputs of a blocking call that has nothing to route
+void ld_host_zero(const shd_route* c, uint32_t flags, uint64_t* edge_out, uint64_t* transit_out, uint64_t* unrouted_out) {
+    if (flags & SHD_ROUTE_LOADS_ADD) return;
+    if (edge_out) std::fill(edge_out, edge_out + c->m, (uint64_t)0);
+    if (transit_out) std::fill(transit_out, transit_out + c->n, (uint64_t)0);
+    if (unrouted_out) *unrouted_out = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_loads_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                          int64_t ld, uint32_t flags, const uint64_t* d_wt, uint64_t* d_edge_load, uint64_t* d_transit,
+                          uint64_t* d_unrouted, void* stream) {
+    if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    int rc = ld_zero(c, flags, d_edge_load, d_transit, d_unrouted, st);
+    if (rc || ns == 0 || nt == 0) return rc;
+    return ld_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, d_wt, flags, d_edge_load, d_transit, d_unrouted,
+                      st);
+}
+
+int shd_route_loads(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
+                    const uint64_t* wt, uint64_t* edge_load_out, uint64_t* transit_out, uint64_t* unrouted_out) {
+    if (!c || ns < 0 || nt < 0 || (ns && !src) || (nt && !tgt)) return SHD_ROUTE_EINVAL;
+    for (int32_t i = 0; i < ns; i++)
+        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
+    for (int32_t j = 0; j < nt; j++)
+        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
+    if (ns == 0 || nt == 0) {
+        ld_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // rows of weights per device chunk: up to 1 GiB
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)nt;
+    const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / row_bytes));
+    DevBuf dsrc, dtgt, dw;
+    LoadsOut out;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * ns)) || (rc = dtgt.alloc(sizeof(int32_t) * nt)) ||
+        (wt && (rc = dw.alloc(row_bytes * chunk))) || (rc = out.init(c)))
+        return rc;
+    if (hipMemcpy(dsrc.p, src, sizeof(int32_t) * ns, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess)
+        return SHD_ROUTE_EDEVICE;
+    int soft = SHD_ROUTE_OK;
+    for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
+        const int32_t k = std::min(chunk, ns - i0);
+        if (wt && hipMemcpy(dw.p, wt + (size_t)i0 * nt, row_bytes * k, hipMemcpyHostToDevice) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        rc = ld_sources(c, (const int32_t*)dsrc.p + i0, k, (const int32_t*)dtgt.p, nt, nt, nullptr,
+                        wt ? (const uint64_t*)dw.p : nullptr, flags, (uint64_t*)out.de.p, (uint64_t*)out.dt.p,
+                        (uint64_t*)out.du.p, nullptr);
+        if (rc) return rc;
+        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
+        if (rc && !soft) soft = rc;
+    }
+    if ((rc = out.finish(flags, edge_load_out, transit_out, unrouted_out))) return rc;
+    return soft;
+}
+
+int shd_route_pair_loads(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, const uint64_t* pair_wt,
+                         int64_t npairs, uint32_t flags, uint64_t* edge_load_out, uint64_t* transit_out,
+                         uint64_t* unrouted_out) {
+    if (!c || npairs < 0 || npairs > 0x7FFFFFFF || (npairs && (!pair_src || !pair_tgt))) return SHD_ROUTE_EINVAL;
+    const int n = c->n;
+    const int np = (int)npairs;
+    for (int k = 0; k < np; k++)
+        if (pair_src[k] < 0 || pair_src[k] >= n || pair_tgt[k] < 0 || pair_tgt[k] >= n) return SHD_ROUTE_EINVAL;
+    if (np == 0) {
+        ld_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // pairs grouped by source, as shd_route_paths groups them: the entries of distinct source
+    // u are the grouped positions eoff[u] .. eoff[u + 1]
+    std::vector<int> order(np);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pair_src[a] < pair_src[b]; });
+    std::vector<int32_t> us, gt(np);
+    std::vector<uint64_t> gw(pair_wt ? np : 0);
+    std::vector<long long> eoff;
+    for (int g = 0; g < np; g++) {
+        const int32_t s = pair_src[order[g]];
+        if (us.empty() || us.back() != s) { us.push_back(s); eoff.push_back(g); }
+        gt[g] = pair_tgt[order[g]];
+        if (pair_wt) gw[g] = pair_wt[order[g]];
+    }
+    eoff.push_back(np);
+    const int nu = (int)us.size();
+    DevBuf dsrc, dtgt, dw, doff;
+    LoadsOut out;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
+        (pair_wt && (rc = dw.alloc(sizeof(uint64_t) * (size_t)np))) ||
+        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) || (rc = out.init(c)))
+        return rc;
+    if (hipMemcpy(dsrc.p, us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
+        (pair_wt && hipMemcpy(dw.p, gw.data(), sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(doff.p, eoff.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess)
+        return SHD_ROUTE_EDEVICE;
+    rc = ld_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, 0, (const long long*)doff.p,
+                    pair_wt ? (const uint64_t*)dw.p : nullptr, flags, (uint64_t*)out.de.p, (uint64_t*)out.dt.p,
+                    (uint64_t*)out.du.p, nullptr);
+    if (rc) return rc;
+    int soft = shd_route_sync(c, nullptr);
+    if (soft && soft != SHD_ROUTE_ENOEDGE && soft != SHD_ROUTE_EUNREACH) return soft;
+    if ((rc = out.finish(flags, edge_load_out, transit_out, unrouted_out))) return rc;
     return soft;
 }
 

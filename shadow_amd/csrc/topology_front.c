@@ -260,6 +260,7 @@ void shd_topology_free(shd_topology_t* t) {
 }
 
 int32_t shd_topology_vertex_count(const shd_topology_t* t) { return t ? t->n : -1; }
+int32_t shd_topology_edge_count(const shd_topology_t* t) { return t ? t->g.n_edges : -1; }
 
 int32_t shd_topology_find_vertex(const shd_topology_t* t, const char* id) {
     if (!t || !id || !t->gml.vertex_ids) return -1;
@@ -563,6 +564,22 @@ void shd_topology_increment_path_packet_counter(shd_topology_t* t, int32_t s, in
     pthread_mutex_unlock(&c->pc[st].lock);
 }
 
+void shd_topology_add_path_packets(shd_topology_t* t, int32_t s, int32_t d, uint64_t packets) {
+    pcache* c;
+    int64_t k = entry(t, s, d, &c);
+    if (k < 0 || !packets) return;
+    /* the low word on the pair's own counter, a wrap of it and the high word on the spill */
+    const uint32_t lo = (uint32_t)packets;
+    uint64_t hi = packets >> 32;
+    if (lo && (uint64_t)__atomic_fetch_add(&c->cnt[k], lo, __ATOMIC_RELAXED) + lo > UINT32_MAX) hi++;
+    if (!hi) return;
+    const uint64_t key = (uint64_t)k + 1;
+    const unsigned st = pc_stripe(key);
+    pthread_mutex_lock(&c->pc[st].lock);
+    *pc_slot(&c->pc[st], key) += hi << 32;
+    pthread_mutex_unlock(&c->pc[st].lock);
+}
+
 uint64_t shd_topology_get_path_packet_count(shd_topology_t* t, int32_t s, int32_t d) {
     pcache* c;
     int64_t k = entry(t, s, d, &c);
@@ -719,6 +736,84 @@ int shd_topology_dump_routes(shd_topology_t* t, FILE* out) {
         }
     }
     free(ps); free(pt); free(pi); free(pj); free(off); free(vert); free(edge); free(hl); free(line);
+    return rc;
+}
+
+/* ---- link loads: the cached Paths' packet counters summed per edge and per vertex
+ * (shd_route_pair_loads on engine 0, nothing cached) ---- */
+
+int shd_topology_link_loads(shd_topology_t* t, uint64_t* edge_packets, uint64_t* transit_packets, uint64_t* unrouted) {
+    if (!t) return SHD_ROUTE_EINVAL;
+    if (edge_packets) memset(edge_packets, 0, sizeof(uint64_t) * (size_t)t->g.n_edges);
+    if (transit_packets) memset(transit_packets, 0, sizeof(uint64_t) * (size_t)t->n);
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    /* the counters live in the current fill, or between a late attach and the next lookup in
+     * the fill it retired; before the first fill there are none */
+    pcache* c = t->cache ? t->cache : t->retired;
+    int rc = SHD_ROUTE_OK;
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0, pcap = 0;
+    if (c) {
+        /* every pair with a non-zero count: the dense u32 counter plus its spill, the stripes
+         * locked once for the pass as carry_counters locks them */
+        for (int k = 0; k < PC_STRIPES; k++) pthread_mutex_lock(&c->pc[k].lock);
+        for (int32_t i = 0; i < c->na && !rc; i++)
+            for (int32_t j = i; j < c->na; j++) {
+                const size_t k = tri(c->na, i, j);
+                uint64_t v = __atomic_load_n(&c->cnt[k], __ATOMIC_RELAXED);
+                const pcmap* m = &c->pc[pc_stripe((uint64_t)k + 1)];
+                if (m->cap) {
+                    size_t h = (((uint64_t)k + 1) * 0x9E3779B97F4A7C15ull) & (m->cap - 1);
+                    while (m->s[h].key && m->s[h].key != (uint64_t)k + 1) h = (h + 1) & (m->cap - 1);
+                    if (m->s[h].key) v += m->s[h].val;
+                }
+                if (!v) continue;
+                if (np == pcap) {
+                    pcap = pcap ? 2 * pcap : 1024;
+                    int32_t* s2 = realloc(ps, sizeof(int32_t) * pcap);
+                    if (s2) ps = s2;
+                    int32_t* t2 = realloc(pt, sizeof(int32_t) * pcap);
+                    if (t2) pt = t2;
+                    uint64_t* w2 = realloc(pw, sizeof(uint64_t) * pcap);
+                    if (w2) pw = w2;
+                    if (!s2 || !t2 || !w2) { rc = SHD_ROUTE_ENOMEM; break; }
+                }
+                ps[np] = c->A[i]; pt[np] = c->A[j]; pw[np] = v;  /* stored orientation: lower -> higher */
+                np++;
+            }
+        for (int k = PC_STRIPES - 1; k >= 0; k--) pthread_mutex_unlock(&c->pc[k].lock);
+    }
+    if (!rc && np) {
+        rc = shd_route_pair_loads(t->eng[0], ps, pt, pw, (int64_t)np, SHD_ROUTE_DISPATCH, edge_packets, transit_packets,
+                                  unrouted);
+        /* ENOEDGE: a self pair without a self-loop, stored as the path to self; its packets
+         * are in *unrouted */
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;
+    }
+    pthread_mutex_unlock(&t->lock);
+    free(ps); free(pt); free(pw);
+    return rc;
+}
+
+int shd_topology_dump_link_loads(shd_topology_t* t, FILE* out) {
+    if (!t || !out) return SHD_ROUTE_EINVAL;
+    const int32_t m = t->g.n_edges;
+    uint64_t* ep = malloc(sizeof(uint64_t) * ((size_t)m + 1));
+    if (!ep) return SHD_ROUTE_ENOMEM;
+    int rc = shd_topology_link_loads(t, ep, NULL, NULL);
+    char* line = NULL;
+    size_t lcap = 0;
+    for (int32_t e = 0; e < m && !rc; e++) {
+        if (!ep[e]) continue;
+        const int64_t len = shd_topology_link_line(&line, &lcap, t->gml.vertex_ids, e, t->g.edge_src[e], t->g.edge_dst[e],
+                                                   t->g.edge_latency[e], t->g.edge_packetloss[e], ep[e], t->directed);
+        if (len < 0) { rc = SHD_ROUTE_ENOMEM; break; }
+        fwrite(line, 1, (size_t)len, out);
+        fputc('\n', out);
+    }
+    free(line); free(ep);
     return rc;
 }
 

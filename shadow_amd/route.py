@@ -28,6 +28,7 @@ PLAN_REUSE = 0x200  # shd_route.h SHD_ROUTE_PLAN_REUSE
 REFRESH_ALL, REFRESH_MINE, REFRESH_JOBS = 0x1, 0x2, 0x4  # SHD_ROUTE_REFRESH_*
 PAYLOAD_LAT16 = 0x1
 FILL_LAT16 = 0x100
+LOADS_ADD = 0x400  # shd_route.h SHD_ROUTE_LOADS_ADD
 
 
 class RouteError(RuntimeError):
@@ -83,7 +84,7 @@ EXPORTS = (
     "shd_route_kd_stats", "shd_route_host_alloc_lazy", "shd_route_host_wait",
     "shd_route_host_unpinned", "shd_route_plan_refresh_async", "shd_route_plan_landmarks",
     "shd_route_plan_bind_store", "shd_route_hops_async", "shd_route_hops", "shd_route_paths",
-    "shd_route_plan_jobs",
+    "shd_route_plan_jobs", "shd_route_loads_async", "shd_route_loads", "shd_route_pair_loads",
 )
 
 _lib = None
@@ -162,6 +163,12 @@ def load_library():
     L.shd_route_hops.argtypes = [P, P, I32, P, I32, U32, P, P]
     L.shd_route_paths.restype = C.c_int
     L.shd_route_paths.argtypes = [P, P, P, I64, U32, P, P, P, I64]
+    L.shd_route_loads_async.restype = C.c_int
+    L.shd_route_loads_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P, P]
+    L.shd_route_loads.restype = C.c_int
+    L.shd_route_loads.argtypes = [P, P, I32, P, I32, U32, P, P, P, P]
+    L.shd_route_pair_loads.restype = C.c_int
+    L.shd_route_pair_loads.argtypes = [P, P, P, P, I64, U32, P, P, P]
     _lib = L
     return L
 
@@ -306,7 +313,66 @@ class RouteEngine:
         _check(rc, "shd_route_paths")
         return off, vert, edge
 
+    def _loads_out(self, out):
+        if out is not None:
+            return out
+        return (np.zeros(self.info["n_edges"], np.uint64), np.zeros(self.info["n_vertices"], np.uint64),
+                np.zeros(1, np.uint64))
+
+    def loads(self, sources, targets, weights=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_loads: (edge_load, transit, unrouted) of the (source, target) block, uint64:
+        the weight each edge id carries, the weight through each vertex as an intermediate hop,
+        and the summed weight of the failed entries.  weights: (sources, targets) uint64, None =
+        1 per entry.  out: the three arrays of an earlier call (unrouted as a 1-element array)
+        to write into; add=True (SHD_ROUTE_LOADS_ADD) adds into them.  A missing self-loop or an
+        unreachable target raises RouteError; ``err.partial`` then holds the results."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        el, tr, un = self._loads_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_loads(self._h, _p(s), len(s), _p(t), len(t), flags, _p(w), _p(el), _p(tr), _p(un))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_loads")
+            err.partial = (el, tr, int(un[0]))
+            raise err
+        _check(rc, "shd_route_loads")
+        return el, tr, int(un[0])
+
+    def pair_loads(self, pair_src, pair_tgt, pair_wt=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_pair_loads: as loads() for a list of (source, target, weight) pairs in any
+        order, repeats adding up (pair_wt None = 1 each)."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        el, tr, un = self._loads_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_pair_loads(self._h, _p(s), _p(t), _p(w), len(s), flags, _p(el), _p(tr), _p(un))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_loads")
+            err.partial = (el, tr, int(un[0]))
+            raise err
+        _check(rc, "shd_route_pair_loads")
+        return el, tr, int(un[0])
+
     # -- device-pointer API (torch tensors as HBM plumbing) --------------------
+    def loads_async(self, d_src, d_tgt, d_wt, d_edge_load, d_transit, d_unrouted, stream=None, dispatch=True,
+                    ld=None, add=False):
+        """shd_route_loads_async over device tensors: int32 sources and targets, 64-bit weights
+        (None = 1 per entry) and outputs (n_edges, n_vertices, 1 elements; any may be None; the
+        values are unsigned, whatever 64-bit integer dtype carries them)."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_loads_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0),
+            ptr(d_wt), ptr(d_edge_load), ptr(d_transit), ptr(d_unrouted), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_loads_async")
+
     def hops_async(self, d_src, d_tgt, d_hops, d_rowmax, stream=None, dispatch=True, ld=None):
         """shd_route_hops_async over int32 device tensors (d_hops / d_rowmax may be None)."""
         ns, nt = int(d_src.numel()), int(d_tgt.numel())

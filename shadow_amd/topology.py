@@ -29,6 +29,8 @@ EXPORTS = (
     "shd_topology_fill", "shd_topology_dump_paths", "shd_topology_triangle_bytes",
     "shd_attach_create", "shd_attach_find_vertex", "shd_attach_destroy", "shd_topology_attach",
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
+    "shd_topology_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
+    "shd_topology_edge_count", "shd_topology_add_path_packets",
 )
 
 VATTRS = ("ip", "citycode", "countrycode", "geocode", "type")  # SHD_VATTR_* order
@@ -64,6 +66,8 @@ def load_library():
     L.shd_topology_free.argtypes = [P]
     L.shd_topology_vertex_count.restype = I32
     L.shd_topology_vertex_count.argtypes = [P]
+    L.shd_topology_edge_count.restype = I32
+    L.shd_topology_edge_count.argtypes = [P]
     L.shd_topology_find_vertex.restype = I32
     L.shd_topology_find_vertex.argtypes = [P, C.c_char_p]
     L.shd_topology_attach_vertex.restype = C.c_int
@@ -78,6 +82,7 @@ def load_library():
     L.shd_topology_is_direct_path.restype = C.c_int
     L.shd_topology_is_direct_path.argtypes = [P, I32, I32]
     L.shd_topology_increment_path_packet_counter.argtypes = [P, I32, I32]
+    L.shd_topology_add_path_packets.argtypes = [P, I32, I32, C.c_uint64]
     L.shd_topology_get_path_packet_count.restype = C.c_uint64
     L.shd_topology_get_path_packet_count.argtypes = [P, I32, I32]
     L.shd_topology_min_path_latency.restype = D
@@ -98,6 +103,13 @@ def load_library():
     L.shd_topology_dump_routes.argtypes = [P, P]
     L.shd_topology_route_line.restype = C.c_int64
     L.shd_topology_route_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, P, I32, P, P, D, D, C.c_int]
+    L.shd_topology_link_loads.restype = C.c_int
+    L.shd_topology_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_dump_link_loads.restype = C.c_int
+    L.shd_topology_dump_link_loads.argtypes = [P, P]
+    L.shd_topology_link_line.restype = C.c_int64
+    L.shd_topology_link_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, I32, I32, I32, D, D,
+                                         C.c_uint64, C.c_int]
     S = C.c_char_p
     L.shd_attach_create.restype = C.c_int
     L.shd_attach_create.argtypes = [C.POINTER(P), C.POINTER(_GraphML)]
@@ -231,6 +243,9 @@ class Topology:
     def vertex_count(self):
         return load_library().shd_topology_vertex_count(self._h)
 
+    def edge_count(self):
+        return load_library().shd_topology_edge_count(self._h)
+
     def find_vertex(self, graphml_id: str) -> int:
         return load_library().shd_topology_find_vertex(self._h, graphml_id.encode())
 
@@ -282,6 +297,9 @@ class Topology:
     def increment_path_packet_counter(self, s, d):
         load_library().shd_topology_increment_path_packet_counter(self._h, int(s), int(d))
 
+    def add_path_packets(self, s, d, packets: int):
+        load_library().shd_topology_add_path_packets(self._h, int(s), int(d), int(packets))
+
     def packet_count(self, s, d) -> int:
         return int(load_library().shd_topology_get_path_packet_count(self._h, int(s), int(d)))
 
@@ -316,8 +334,7 @@ class Topology:
                 return buf.value.decode()
             size = k + 1
 
-    def dump_routes(self, path: str):
-        """shd_topology_dump_routes into the file `path`."""
+    def _dump(self, name: str, path: str):
         libc = C.CDLL(None)
         libc.fopen.restype = C.c_void_p
         libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
@@ -326,11 +343,33 @@ class Topology:
         if not fp:
             raise OSError(f"cannot open {path}")
         try:
-            rc = load_library().shd_topology_dump_routes(self._h, fp)
+            rc = getattr(load_library(), "shd_topology_" + name)(self._h, fp)
         finally:
             libc.fclose(fp)
         if rc:
-            raise RuntimeError(f"dump_routes failed ({rc})")
+            raise RuntimeError(f"{name} failed ({rc})")
+
+    def dump_routes(self, path: str):
+        """shd_topology_dump_routes into the file `path`."""
+        self._dump("dump_routes", path)
+
+    def link_loads(self):
+        """shd_topology_link_loads: (edge_packets, transit_packets, unrouted), the cached Paths'
+        packet counters summed per edge id and per intermediate vertex, and the
+        packets of self pairs stored as the path to self."""
+        L = load_library()
+        ep = np.zeros(int(L.shd_topology_edge_count(self._h)), np.uint64)
+        tp = np.zeros(int(L.shd_topology_vertex_count(self._h)), np.uint64)
+        un = C.c_uint64()
+        rc = L.shd_topology_link_loads(self._h, C.c_void_p(ep.ctypes.data), C.c_void_p(tp.ctypes.data), C.byref(un))
+        if rc:
+            raise RuntimeError(f"link_loads failed ({rc})")
+        return ep, tp, int(un.value)
+
+    def dump_link_loads(self, path: str):
+        """shd_topology_dump_link_loads into the file `path`: one line per edge that carried
+        packets."""
+        self._dump("dump_link_loads", path)
 
     def table(self, vertices):
         """Dense lookup(i, j) table (lat, rel) for a vertex list, via the public getters."""
