@@ -334,6 +334,14 @@ int shd_route_plan_bind_store(shd_route_t* ctx, shd_route_plan_t* plan, uint16_t
  * are held whole in HBM (2 x 8 x rows x na bytes + 2 GiB; C4 on one GPU: 41 GB): a
  * larger request is SHD_ROUTE_ENOMEM (shard it over more devices).
  *
+ * SHD_ROUTE_FILL_STAGE in the environment (tests: many stage chunks and reused staging
+ * buffers on a small triangle) sets the pairs per staging buffer: unset, empty, not a
+ * number or <= 0 keeps the default 32 Mi (512 MiB per buffer); the value in effect is never
+ * below one whole row (na pairs; ceil(na / 6) lines in the compact layout) and is rounded
+ * up to a multiple of 4, and the two staging allocations and the free-memory guard
+ * (2 x table + 4 x 8 x stage pairs + 1 GiB) use it.  The schedule itself -- stage chunks,
+ * buffers, copy pieces -- is the pure host function of shadow_amd/csrc/fill_sched.hpp.
+ *
  * With SHD_ROUTE_FILL_LAT16 in flags the triangle is the compact layout instead (10.7 B per
  * pair against 16): row i starts a 64-byte line at line shd_route_tri16_line(na, i), and
  * its pairs j >= i go six to a line, pair e = j - i in line row_start + e / 6 at slot
@@ -386,7 +394,13 @@ int shd_route_tri_payload_async(shd_route_t* ctx, const double* d_lat, const dou
  * chunk is settled, including a chunk the runtime refused to register (it stays pageable:
  * the fill's copies into it still complete, slower); shd_route_host_unpinned(p) waits the
  * same way and returns how many bytes of p stayed pageable (0 = all pinned; for memory not
- * from these allocators, 0).  shd_route_host_free takes either. */
+ * from these allocators, 0).  shd_route_host_free takes either.
+ *
+ * SHD_ROUTE_HOST_CHUNK in the environment (tests: registration boundaries inside a small
+ * triangle) replaces the 256 MiB: bytes per chunk, read when a buffer is allocated, rounded up
+ * to a multiple of 2 MiB (the huge page the mapping is aligned to; 2 MiB at least); unset,
+ * empty, not a number or <= 0 keeps 256 MiB.  SHD_ROUTE_REGFAIL_CHUNK=k leaves chunk k of a
+ * lazy buffer unregistered, as when the runtime refuses it. */
 void* shd_route_host_alloc(size_t bytes);
 void* shd_route_host_alloc_lazy(size_t bytes);
 int shd_route_host_wait(void* p);

@@ -23,6 +23,7 @@
 #include "fw.hpp"
 #include "path_hops.hpp"
 #include "link_loads.hpp"
+#include "fill_sched.hpp"
 
 using namespace shd;
 
@@ -1650,7 +1651,9 @@ struct HostMap {
     size_t maplen = 0;
     char* p = nullptr;     // the caller's pointer (2 MiB aligned)
     size_t len = 0;
-    size_t chunk = (size_t)256 << 20;
+    // (SHD_ROUTE_HOST_CHUNK, read at each allocation: registration boundaries inside a small
+    // triangle -- the fill tests)
+    size_t chunk = shd::fill_host_chunk(getenv("SHD_ROUTE_HOST_CHUNK"));
     int nchunk = 0;
     std::unique_ptr<std::atomic<int>[]> state;  // per chunk: 0 pending, 1 registered, 2 not registered
     bool whole = false;    // eager form: chunks are only first-touched (state 1 = touched), then
@@ -1832,23 +1835,20 @@ int shd_route_fill_triangle(shd_route_t* c, const int32_t* A, int32_t na, int32_
     std::unique_ptr<shd_route_plan, void (*)(shd_route_plan*)> guard(P, shd_route_plan_destroy);
     const int nr = (int)P->row_pos.size();
     if (nr == 0) return SHD_ROUTE_OK;
-    // triangle offsets of this rank's rows (host: pair index of (i, i)), their sizes
-    std::vector<long long> off(nr + 1);
-    auto tri0 = [&](long long i) { return i * (long long)na - i * (i - 1) / 2; };
-    for (int r = 0; r < nr; r++) off[r] = tri0(P->row_pos[r]);
-    off[nr] = off[nr - 1] + (na - P->row_pos[nr - 1]);
-    std::vector<long long> roff(nr + 1, 0);  // packed offsets (pairs) in plan row order
-    for (int r = 0; r < nr; r++) roff[r + 1] = roff[r] + (na - P->row_pos[r]);
-    // the compact layout in 64-byte lines: triangle line of each row, packed lines in row order
-    std::vector<long long> loff(nr + 1), rline(nr + 1, 0);
-    if (l16) {
-        for (int r = 0; r < nr; r++) loff[r] = shd_route_tri16_line(na, P->row_pos[r]);
-        for (int r = 0; r < nr; r++) rline[r + 1] = rline[r] + (na - P->row_pos[r] + 5) / 6;
-    }
+    // the schedule (fill_sched.hpp): stage chunks of plan rows, their copy pieces cut at the
+    // chunk boundaries of shd_route_host_alloc's memory (a copy waits for the chunks it lands
+    // in to be pinned, and never spans two: each is its own registration), and the packed
+    // offset of each row in pairs, or in 64-byte lines for the compact layout
+    std::vector<int> posv(P->row_pos.begin(), P->row_pos.end());
+    const std::shared_ptr<HostMap> hm = host_map_of(lr_out);
+    const size_t host_off = hm ? (size_t)((char*)lr_out - hm->p) : 0;
+    // (SHD_ROUTE_FILL_STAGE: the pairs per staging buffer, for tests with many stage chunks)
+    const size_t stage_pairs = (size_t)shd::fill_stage_pairs(getenv("SHD_ROUTE_FILL_STAGE"), na, l16);
+    const shd::FillSchedule sched = shd::fill_schedule(na, posv.data(), nr, l16, shd::fill_stage_units((long long)stage_pairs, l16),
+                                                       hm ? hm->chunk : 0, host_off);
     const size_t table = sizeof(double) * (size_t)nr * (size_t)na;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    const size_t stage_pairs = (size_t)32 << 20;  // 512 MiB of (lat, rel) per staging buffer
     if (2 * table + 4 * stage_pairs * 8 + ((size_t)1 << 30) > fr) return SHD_ROUTE_ENOMEM;
     DevBuf dtgt, dlat, drel, dpos, doff, dstage[2], dmn;
     if ((rc = dtgt.alloc(sizeof(int32_t) * na)) || (rc = dlat.alloc(table)) || (rc = drel.alloc(table)) ||
@@ -1860,13 +1860,10 @@ int shd_route_fill_triangle(shd_route_t* c, const int32_t* A, int32_t na, int32_
     if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&xs, hipStreamNonBlocking) != hipSuccess)
         return SHD_ROUTE_EDEVICE;
-    std::vector<int> posv(P->row_pos.begin(), P->row_pos.end());
     bool ok = hipMemcpy(dtgt.p, A, sizeof(int32_t) * na, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(dpos.p, posv.data(), sizeof(int) * nr, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(doff.p, roff.data(), sizeof(long long) * (nr + 1), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(doff.p, sched.pk.data(), sizeof(long long) * (nr + 1), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemsetAsync(dmn.p, 0xFF, sizeof(unsigned long long), cs) == hipSuccess;
-    if (ok && l16)
-        ok = hipMemcpy(doff.p, rline.data(), sizeof(long long) * (nr + 1), hipMemcpyHostToDevice) == hipSuccess;
     // (the plan was made just now: its landmark rows, if any, are current)
     if (ok) rc = shd_route_rows_planned_async(c, P, (const int32_t*)dtgt.p, na, na, flags | SHD_ROUTE_PLAN_REUSE, (double*)dlat.p,
                                               (double*)drel.p, nullptr, cs);
@@ -1875,30 +1872,11 @@ int shd_route_fill_triangle(shd_route_t* c, const int32_t* A, int32_t na, int32_
     // rows in triangle order (one rank) a chunk is one contiguous range of the cache
     hipEvent_t packed[2], copied[2];
     for (int b = 0; b < 2; b++) { (void)hipEventCreateWithFlags(&packed[b], hipEventDisableTiming); (void)hipEventCreateWithFlags(&copied[b], hipEventDisableTiming); }
-    int buf = 0;
     bool first[2] = {true, true};
-    // into memory of shd_route_host_alloc_lazy: a copy waits for the chunks it lands in to be
-    // pinned, and never spans two chunks (each is its own registration)
-    const std::shared_ptr<HostMap> hm = host_map_of(lr_out);
-    auto copy_out = [&](char* dst, const char* src, size_t bytes) {
-        while (bytes) {
-            size_t nb = bytes;
-            if (hm) {
-                const size_t o = (size_t)(dst - hm->p);
-                nb = std::min(nb, (o / hm->chunk + 1) * hm->chunk - o);
-                hm->wait_range(o, nb);
-            }
-            if (hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToHost, xs) != hipSuccess) return false;
-            dst += nb; src += nb; bytes -= nb;
-        }
-        return true;
-    };
-    const std::vector<long long>& pk = l16 ? rline : roff;  // packed units: lines or pairs
-    const long long stage_units = l16 ? (long long)(16 * stage_pairs / 64) : (long long)stage_pairs;
-    for (int r0 = 0; r0 < nr && !rc; buf ^= 1) {
-        int r1 = r0;
-        while (r1 < nr && pk[r1 + 1] - pk[r0] <= stage_units) r1++;
-        if (r1 == r0) r1 = r0 + 1;  // (a row longer than a stage buffer cannot happen: na < 2^25)
+    for (size_t k = 0; k < sched.chunks.size() && !rc; k++) {
+        const shd::FillChunk& ch = sched.chunks[k];
+        const int r0 = ch.r0, r1 = ch.r1, buf = ch.buf;
+        // (a row longer than a stage buffer cannot happen: the stage holds one row at least)
         if (!first[buf] && hipStreamWaitEvent(cs, copied[buf], 0) != hipSuccess) { rc = SHD_ROUTE_EDEVICE; break; }
         first[buf] = false;
         if (l16)
@@ -1912,28 +1890,16 @@ int shd_route_fill_triangle(shd_route_t* c, const int32_t* A, int32_t na, int32_
         if (hipGetLastError() != hipSuccess || hipEventRecord(packed[buf], cs) != hipSuccess ||
             hipStreamWaitEvent(xs, packed[buf], 0) != hipSuccess) { rc = SHD_ROUTE_EDEVICE; break; }
         // copy: consecutive rows with consecutive triangle offsets go out in one piece
-        for (int a = r0; a < r1;) {
-            int b = a + 1;
-            if (l16) {
-                while (b < r1 && loff[b] == loff[b - 1] + (na - P->row_pos[b - 1] + 5) / 6) b++;
-                const size_t lines = (size_t)(rline[b] - rline[a]);
-                if (!copy_out((char*)lr_out + 64 * loff[a], (char*)dstage[buf].p + 64 * (rline[a] - rline[r0]), 64 * lines)) {
-                    rc = SHD_ROUTE_EDEVICE;
-                    break;
-                }
-            } else {
-                while (b < r1 && off[b] == off[b - 1] + (na - P->row_pos[b - 1])) b++;
-                const size_t pairs = (size_t)(roff[b] - roff[a]);
-                if (!copy_out((char*)(lr_out + 2 * off[a]), (char*)((double*)dstage[buf].p + 2 * (roff[a] - roff[r0])),
-                              16 * pairs)) {
-                    rc = SHD_ROUTE_EDEVICE;
-                    break;
-                }
+        for (int q = ch.p0; q < ch.p1; q++) {
+            const shd::FillPiece& pc = sched.pieces[q];
+            if (hm) hm->wait_range(host_off + (size_t)pc.dst, (size_t)pc.bytes);
+            if (hipMemcpyAsync((char*)lr_out + pc.dst, (const char*)dstage[buf].p + pc.src, (size_t)pc.bytes,
+                               hipMemcpyDeviceToHost, xs) != hipSuccess) {
+                rc = SHD_ROUTE_EDEVICE;
+                break;
             }
-            a = b;
         }
         if (hipEventRecord(copied[buf], xs) != hipSuccess) rc = SHD_ROUTE_EDEVICE;
-        r0 = r1;
     }
     if (hipStreamSynchronize(cs) != hipSuccess || hipStreamSynchronize(xs) != hipSuccess) rc = rc ? rc : SHD_ROUTE_EDEVICE;
     for (int b = 0; b < 2; b++) { (void)hipEventDestroy(packed[b]); (void)hipEventDestroy(copied[b]); }

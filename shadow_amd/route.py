@@ -419,13 +419,15 @@ class RouteEngine:
         """shd_route_fill_triangle: this rank's rows of the front end's upper-triangle cache
         over the sorted `attached` vertices into `out` (a PinnedBuffer or any object with
         .ptr; 16 * na * (na + 1) / 2 bytes, or 64 * tri16_lines(na) with lat16: the compact
-        layout).  Returns (min latency written, seconds)."""
+        layout).  Returns (min latency written, seconds); ``self.last_fill_code`` is the
+        call's code: OK, or ENOEDGE / EUNREACH when entries failed (they are NaN / 0xFFFF)."""
         A = np.ascontiguousarray(attached, np.int32)
         mn, sec = C.c_double(), C.c_double()
         flags = (DISPATCH if dispatch else 0) | (FILL_LAT16 if lat16 else 0)
         rc = load_library().shd_route_fill_triangle(self._h, _p(A), len(A), int(world), int(rank),
                                                    flags, C.c_void_p(out.ptr),
                                                    C.byref(mn), C.byref(sec))
+        self.last_fill_code = rc
         if rc not in (OK, ENOEDGE, EUNREACH):
             raise RouteError(rc, "shd_route_fill_triangle")
         return mn.value, sec.value

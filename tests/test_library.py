@@ -139,3 +139,38 @@ def test_plan_scheduler_standalone_sanitized(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout, r.stderr)
     assert r.stdout.strip() == "ok 900 schedules", r.stdout
+
+
+def test_fill_schedule_standalone_sanitized(tmp_path):
+    """The schedule of shd_route_fill_triangle (shadow_amd/csrc/fill_sched.hpp: pure host code)
+    with tests/fill_sched_main.cpp, built with -fsanitize=address,undefined and run as its own
+    process: 1080 random rank shares (na 1 to ~3000, world 1 to 8, both layouts, stages from one
+    row to everything, host chunks of 0, 2 and 6 MiB) against a brute-force byte map of the
+    triangle, and the default constants at the C3 and C4 sizes, whose chunk, buffer-reuse and
+    copy-piece counts the output line puts on record (C4, one rank: 38 chunks interleaved, 25
+    compact -- 36 and 23 packs of a staging buffer that was copied out before)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    for extra in (["-static-libasan", "-static-libubsan"], []):
+        san = ["-fsanitize=address,undefined", "-fno-sanitize-recover", *extra]
+        if subprocess.run([cxx, *san, "-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode == 0:
+            break
+    else:
+        pytest.skip("g++ lacks the sanitizer runtime")
+    exe = tmp_path / "fill_sched_test"
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", *san, "-o", str(exe),
+                    os.path.join(ROOT, "tests", "fill_sched_main.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    print(r.stdout.strip())
+    m = re.fullmatch(r"ok 1088 schedules; c3 interleaved 2 chunks 0 reuses \d+ pieces compact 1 chunks 0 reuses \d+ pieces "
+                     r"world2 .*, c4 interleaved 38 chunks 36 reuses \d+ pieces compact 25 chunks 23 reuses \d+ pieces "
+                     r"world8 interleaved (\d+) chunks (\d+) reuses \d+ pieces world8 compact (\d+) chunks (\d+) reuses \d+ pieces",
+                     r.stdout.strip())
+    assert m, r.stdout
+    assert int(m.group(1)) - 2 == int(m.group(2)) >= 1 and int(m.group(3)) - 2 == int(m.group(4)) >= 1
