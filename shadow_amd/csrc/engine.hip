@@ -24,6 +24,7 @@
 #include "path_hops.hpp"
 #include "link_loads.hpp"
 #include "fill_sched.hpp"
+#include "select.hpp"
 
 using namespace shd;
 
@@ -98,46 +99,26 @@ struct shd_route {
     char* d_ws = nullptr; size_t ws_stride = 0; int ws_slots = 0;
     bool lds = false;
     size_t lds_bytes = 0;
-    // K32 integer fast path (sssp_k32.hpp)
-    int k32 = 0, k32_block = 256, k32_bound = 0;
-    size_t k32_lds = 0;
-    int* d_k32_row_in = nullptr;
-    ArcRec* d_arc = nullptr;
-    uint16_t* d_k32_col_in = nullptr;
-    double* d_k32_r_in = nullptr;
+    // the rows kernel chosen at creation and what it reads (select.hpp; apply_selection):
+    // sel 0 f64, 1 K32 (sssp_k32.hpp), 2 KB (sssp_batch.hpp) + K2 path attributes
+    // (path_attr.hpp), 4 KD (sssp_delta.hpp), 5 KF (sssp_f64d.hpp); 3 was the retired K16
+    int sel = 0;
+    InRows inrows;
+    K32Choice k32;
+    AttrChoice attr;
+    KBChoice kb;
+    KDChoice kd;
+    KFChoice kf;
     unsigned long long* d_dbg = nullptr;  // SHD_STAMPS builds: per-source phase stamps
-    // KB batched kernel (sssp_batch.hpp) + K2 path attributes (path_attr.hpp)
-    int kb = 0, attr = 0, kb_nseg = 0, kb_nhub = 0, kb_npart = 0;
-    size_t kb_lds = 0, attr_lds = 0;
-    uint32_t* d_kb_arc = nullptr;
-    KBSeg* d_kb_seg = nullptr;
-    KBHub* d_kb_hub = nullptr;
-    int kb_fused = 0, kbf_nrtab = 0, kb_grid_cap = 0, kbf_tcap = 0;  // sssp_batch_kernel<true>: rows in one kernel
-    size_t kbf_lds = 0;
-    uint32_t* d_kbf_arc = nullptr;    // in-arcs u << 16 | ridx << 8 | w
-    double* d_kbf_rtab = nullptr;     // distinct reliabilities
-    uint32_t* d_keys = nullptr;     // key rows scratch (ns x n u32), grown on demand
+    uint32_t* d_keys = nullptr;     // KB key rows scratch (ns x n u32), grown on demand
     size_t keys_cap = 0;
-    // KD delta-stepping kernel (sssp_delta.hpp)
-    int kd = 0, kd_block = 1024, kd_slots = 0, kd_delta = 1, kd_qcap = 0;
-    size_t kd_lds = 0, kd_stride = 0;
-    // the planner's unseeded hub rows on 256-thread contexts (C3): 1024-thread workgroups,
-    // one row per CU, cut the latency of that launch (each row is unseeded and alone)
-    int kd_hub_block = 0, kd_hub_qcap = 0, kd_hub_delta = 1;
-    size_t kd_hub_lds = 0;
-    int* d_kd_lstart = nullptr;   // light in-CSR offsets (n+1)
-    uint32_t* d_kd_orec = nullptr;  // out-arc records v | w << 16
-    uint16_t* d_kd_oridx = nullptr; // rtab index per out-arc
-    uint32_t* d_kd_lrec = nullptr;  // light in-arc records (2 x u32 per arc)
-    double* d_kd_rtab = nullptr;    // distinct reliabilities
-    int kd_nlight = 0, kd_nrtab = 1, kd_walk = 0, kd_packed = 0, kd_fused = 0;
-    int has_vf = 0;  // some vertex has a packet-loss factor (else f_v is absent everywhere)
-    int vf_lossy = 0;  // some vertex factor is not exactly 1.0 (else every present f_v is a no-op)
-    int kd_rone = -1;  // rtab index of exactly 1.0 (-1: none)
-    char* d_kd_ws = nullptr;
-    int* d_fwflag = nullptr;  // K4: per pivot, its closed tile is published (fw_restp_kernel)
+    char* d_kd_ws = nullptr;  // KD: the workgroup slices (kd.stride each, kd.slots of them)
     unsigned long long* d_kd_stats = nullptr;  // KD liveness counters (shd_route_kd_stats)
     int* d_kd_next = nullptr;  // KD source queue counter
+    char* d_kf_ws = nullptr;  // KFH: the workgroup slices of the per-vertex state
+    int has_vf = 0;  // some vertex has a packet-loss factor (else f_v is absent everywhere)
+    int vf_lossy = 0;  // some vertex factor is not exactly 1.0 (else every present f_v is a no-op)
+    int* d_fwflag = nullptr;  // K4: per pivot, its closed tile is published (fw_restp_kernel)
     // host copies for seeded planning (shd_route_plan_*): out-CSR, rtab index per arc and
     // the landmark closeness of every vertex (computed on the first plan)
     std::vector<int> h_row, h_col;
@@ -154,20 +135,6 @@ struct shd_route {
     uint32_t* d_lm_prow = nullptr;
     char* d_hub_ws = nullptr;       // the planner's hub-row launch scratch (kept: a free costs a sync)
     size_t hub_ws_bytes = 0;
-    int sel = 0;  // selected SSSP kernel: 0 f64, 1 K32, 2 KB+K2, 4 KD, 5 KF (3: the retired K16)
-    // KF (fractional latencies, LDS-resident f64 delta-stepping)
-    int kf_block = 0, kf_slots = 0;
-    size_t kf_lds = 0;
-    double kf_delta = 1.0;
-    int kf_nrtab = 0;
-    int kf_h = 0;             // KFH: the per-vertex state in a per-workgroup HBM slice (n > ~12k)
-    char* d_kf_ws = nullptr;
-    size_t kf_ws_stride = 0;
-    uint8_t* d_kf_rix = nullptr;
-    uint32_t* d_kf_opk = nullptr;  // KF packed arcs (head | k << 16, weight k / kf_wscale), or null
-    uint32_t* d_kf_ipk = nullptr;
-    double kf_wscale = 0.0;
-    double* d_kf_rtab = nullptr;
     // K4 (fw.hpp): u16 all-pairs table + dense u16 weights, Np x Np (Np = n rounded to 64)
     uint16_t* d_fwD = nullptr;
     uint32_t* d_fwinl = nullptr;  // K4 parent search: sorted in-arc keys per vertex (np x np)
@@ -200,17 +167,6 @@ namespace {
 
 HostPool* host_pool();  // (plan.hpp; shd_route_create starts the planner's workers)
 
-// KD workgroup sizes: f(std::integral_constant<int, B>) for the runtime block size
-template <typename F>
-auto kd_dispatch(int blk, F f) {
-    switch (blk) {
-        case 1024: return f(std::integral_constant<int, 1024>{});
-        case 768: return f(std::integral_constant<int, 768>{});
-        case 512: return f(std::integral_constant<int, 512>{});
-        default: return f(std::integral_constant<int, 256>{});
-    }
-}
-
 int hip_check(hipError_t e) { return e == hipSuccess ? SHD_ROUTE_OK : SHD_ROUTE_EDEVICE; }
 
 template <typename T>
@@ -231,35 +187,6 @@ DevGraph dev_graph(const shd_route* c) {
     g.row_in = c->d_row_in; g.col_in = c->d_col_in; g.w_in = c->d_w_in; g.r_in = c->d_r_in;
     g.vf = c->d_vf; g.self_w = c->d_self_w; g.self_r = c->d_self_r;
     return g;
-}
-
-// Build a CSR (rows by `key`, columns by `other`), arcs sorted by (row, col, eid).
-void build_csr(int n, const std::vector<int32_t>& rows, const std::vector<int32_t>& cols,
-               const std::vector<int32_t>& eids, const std::vector<double>& lat,
-               const std::vector<double>& rel, std::vector<int>& row, std::vector<int>& col,
-               std::vector<double>& w, std::vector<double>& r, std::vector<int>* eid_out = nullptr) {
-    const size_t k = rows.size();
-    std::vector<size_t> idx(k);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
-        if (rows[a] != rows[b]) return rows[a] < rows[b];
-        if (cols[a] != cols[b]) return cols[a] < cols[b];
-        return eids[a] < eids[b];
-    });
-    row.assign(n + 1, 0);
-    col.resize(k); w.resize(k); r.resize(k);
-    for (size_t q = 0; q < k; q++) {
-        size_t a = idx[q];
-        row[rows[a] + 1]++;
-        col[q] = cols[a];
-        w[q] = lat[eids[a]];
-        r[q] = rel[eids[a]];
-    }
-    if (eid_out) {
-        eid_out->resize(k);
-        for (size_t q = 0; q < k; q++) (*eid_out)[q] = eids[idx[q]];
-    }
-    for (int v = 0; v < n; v++) row[v + 1] += row[v];
 }
 
 bool strongly_connected(int n, const std::vector<int>& row, const std::vector<int>& col,
@@ -310,387 +237,80 @@ int ensure_dense(shd_route* c) {
     return upload(c, &c->d_R, R);
 }
 
-// Host Dijkstra (exact for integer weights) -> eccentricity of vertex 0.
-double ecc0(int n, const std::vector<int>& row, const std::vector<int>& col, const std::vector<double>& w) {
-    std::vector<double> d(n, INFINITY);
-    std::vector<std::pair<double, int>> h;
-    d[0] = 0;
-    h.push_back({0.0, 0});
-    auto cmp = [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; };
-    while (!h.empty()) {
-        std::pop_heap(h.begin(), h.end(), cmp);
-        auto [du, u] = h.back();
-        h.pop_back();
-        if (du > d[u]) continue;
-        for (int a = row[u]; a < row[u + 1]; a++) {
-            double nd = du + w[a];
-            if (nd < d[col[a]]) { d[col[a]] = nd; h.push_back({nd, col[a]}); std::push_heap(h.begin(), h.end(), cmp); }
-        }
-    }
-    double mx = 0;
-    for (double x : d) mx = std::max(mx, x);
-    return mx;
-}
-
-// K32 eligibility + device arrays: in-rows sorted by (-w, u, eid); out-arc records carry
-// the slot of the same arc in its head's in-row.
-int prepare_k32(shd_route* c, const std::vector<int>& row, const std::vector<int>& col,
-                const std::vector<double>& w, const std::vector<int>& eid, const std::vector<int>& row_in,
-                const std::vector<int>& col_in, const std::vector<double>& w_in) {
-    const int n = c->n;
-    const char* force = getenv("SHD_ROUTE_KERNEL");
-    if (force && (!strcmp(force, "f64") || !strcmp(force, "kf"))) return SHD_ROUTE_OK;
-    if (force && !*force) force = nullptr;
-    if (!c->integer_w || n > 65535 || c->multigraph) return SHD_ROUTE_OK;
-    for (int a = 0; a < c->nnz; a++) if (w[a] > 65535.0) return SHD_ROUTE_OK;
-    std::vector<int> indeg(n, 0);
-    for (int a = 0; a < c->nnz; a++) indeg[col[a]]++;
-    for (int v = 0; v < n; v++) if (indeg[v] > 65535) return SHD_ROUTE_OK;
-    const double bound = ecc0(n, row, col, w) + ecc0(n, row_in, col_in, w_in);
-    if (!(bound < 65535.0)) return SHD_ROUTE_OK;
-    const K32Layout L = K32Layout::make(n);
-    size_t lds = 0;
-    int block = 0;
-    for (int b : {256, 512, 1024}) {
-        size_t sm = b == 256 ? k32_small_bytes<256>() : b == 512 ? k32_small_bytes<512>() : k32_small_bytes<1024>();
-        size_t tot = sm + L.total;
-        if (tot > kLdsBudget) continue;
-        int per_cu = (int)(kLdsBudget / tot);
-        if (per_cu * (b / 64) >= 16 || b == 1024) { block = b; lds = tot; break; }
-    }
-    // in-rows: every out-arc a = (u -> v) appears in v's in-row
-    std::vector<int> irow(n + 1, 0);
-    for (int a = 0; a < c->nnz; a++) irow[col[a] + 1]++;
-    for (int v = 0; v < n; v++) irow[v + 1] += irow[v];
-    std::vector<int> order(c->nnz), fill(irow.begin(), irow.end() - 1), src_of(c->nnz);
-    for (int u = 0; u < n; u++)
-        for (int a = row[u]; a < row[u + 1]; a++) { src_of[a] = u; order[fill[col[a]]++] = a; }
-    for (int v = 0; v < n; v++)
-        std::sort(order.begin() + irow[v], order.begin() + irow[v + 1], [&](int x, int y) {
-            if (w[x] != w[y]) return w[x] > w[y];
-            if (src_of[x] != src_of[y]) return src_of[x] < src_of[y];
-            return eid[x] < eid[y];
-        });
-    std::vector<ArcRec> arcs(c->nnz);
-    std::vector<uint16_t> cin(c->nnz);
-    std::vector<double> rin(c->nnz);
-    for (int v = 0; v < n; v++)
-        for (int q = irow[v]; q < irow[v + 1]; q++) {
-            int a = order[q];
-            arcs[a].rslot = (uint16_t)(q - irow[v]);
-            cin[q] = (uint16_t)src_of[a];
-            rin[q] = c->e_rel[eid[a]];
-        }
-    for (int a = 0; a < c->nnz; a++) {
-        arcs[a].col = (uint16_t)col[a];
-        arcs[a].w = (uint16_t)w[a];
-        arcs[a].pad = 0;
-    }
-    int rc = upload(c, &c->d_k32_row_in, irow);
-    if (!rc) rc = upload(c, &c->d_arc, arcs);
-    if (!rc) rc = upload(c, &c->d_k32_col_in, cin);
-    if (!rc) rc = upload(c, &c->d_k32_r_in, rin);
+// Uploads what the selection staged, allocates the chosen kernels' workspaces and counters, raises
+// their dynamic-LDS limits, and stores the choice in the context.
+int apply_selection(shd_route* c, Selection&& s) {
+    int rc = SHD_ROUTE_OK;
+    auto up = [&](const char*, auto& h, auto*& d) { if (!rc) rc = upload(c, &d, h); };
+    auto lds_attr = [&](const void* fn, size_t lds) {
+        return hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    };
+    s.inrows.arrays(up);
+    s.k32.arrays(up);
     if (rc) return rc;
-    c->k32_bound = (int)bound;
-    const bool want_k32 = !force || !strcmp(force, "k32") || !strcmp(force, "auto");
-    (void)0;
-    const bool want_kb = !force || !strcmp(force, "kb") || !strcmp(force, "auto");
-    if (block && want_k32) {
-        const void* fn = block == 256 ? (const void*)sssp_k32_kernel<256>
-                       : block == 512 ? (const void*)sssp_k32_kernel<512> : (const void*)sssp_k32_kernel<1024>;
-        rc = hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (s.k32.ok &&
+        (rc = lds_attr(k32_dispatch(s.k32.block, [](auto B) { return (const void*)sssp_k32_kernel<decltype(B)::value>; }),
+                       s.k32.lds)))
+        return rc;
+    if (s.attr.ok && (rc = lds_attr((const void*)path_attr_kernel<256>, s.attr.lds))) return rc;
+    s.kb.packed_arrays(up);
+    if (rc) return rc;
+    if (s.kd.ok) {
+        s.kd.arrays(up);
         if (rc) return rc;
-        c->k32 = 1; c->k32_block = block; c->k32_lds = lds;
-    }
-    // K2 path attributes: relv f64 + parent u16 per vertex in LDS
-    const AttrLayout AL = AttrLayout::make(n);
-    if (AL.total <= kLdsBudget) {
-        c->attr = 1;
-        c->attr_lds = AL.total;
-        rc = hip_check(hipFuncSetAttribute((const void*)path_attr_kernel<256>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)AL.total));
+        if (hipMalloc((void**)&c->d_kd_ws, s.kd.stride * (size_t)s.kd.slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
+        c->allocs.push_back(c->d_kd_ws);
+        if (hipMalloc((void**)&c->d_kd_next, sizeof(int)) != hipSuccess) return SHD_ROUTE_ENOMEM;
+        c->allocs.push_back(c->d_kd_next);
+        if (hipMalloc((void**)&c->d_kd_stats, sizeof(unsigned long long) * 4) != hipSuccess ||
+            hipMemset(c->d_kd_stats, 0, sizeof(unsigned long long) * 4) != hipSuccess)
+            return SHD_ROUTE_ENOMEM;
+        c->allocs.push_back(c->d_kd_stats);
+        kd_dispatch(s.kd.block, [&](auto B) {
+            if (!(rc = lds_attr((const void*)sssp_delta_kernel<decltype(B)::value>, s.kd.lds)))
+                rc = lds_attr((const void*)kd_plan_rows_kernel<decltype(B)::value>, s.kd.lds);
+            return 0;
+        });
         if (rc) return rc;
+        // (the hub rows are an extra: without their LDS limit the context's own rows serve)
+        if (s.kd.hub_block && lds_attr((const void*)kd_plan_rows_kernel<1024>, s.kd.hub_lds)) {
+            s.kd.hub_block = 0; s.kd.hub_qcap = 0; s.kd.hub_lds = 0; s.kd.hub_delta = 1;
+        }
     }
-    // packed in-arcs (u << 16 | w), rows sorted by (-w, u, eid): KB
-    {
-        std::vector<uint32_t> packed(((size_t)c->nnz + 3) / 4 * 4, 0u);
-        for (int q = 0; q < c->nnz; q++) packed[q] = ((uint32_t)cin[q] << 16) | (uint32_t)w[order[q]];
-        rc = upload(c, &c->d_kb_arc, packed);
+    s.kb.arrays(up);
+    if (!rc && s.kb.ok) rc = lds_attr((const void*)sssp_batch_kernel, s.kb.lds);
+    if (!rc && s.kb.fused) rc = lds_attr((const void*)sssp_batch_rows_kernel, s.kb.f_lds);
+    if (rc) return rc;
+    if (s.kf.ok) {
+        s.kf.arrays(up);
+        if (s.kf.wscale > 0.0 && !s.kf.ipk_own) s.kf.d_ipk = s.kf.d_opk;
+        if (!rc)
+            rc = lds_attr(kf_dispatch(s.kf.block, s.kf.h, s.kf.wscale > 0.0, [](auto B, auto H, auto P) {
+                return (const void*)sssp_f64d_kernel<decltype(B)::value, decltype(H)::value, decltype(P)::value>;
+            }), s.kf.lds);
         if (rc) return rc;
-    }
-    // KD delta-stepping: bucket width ~ the 15th (22nd) percentile of arc latencies (>= 1),
-    // so ~15% (22%) of arcs are light; light in-arcs are the tail of each (-w)-sorted in-row
-    const bool want_kd = !force || !strcmp(force, "kd") || !strcmp(force, "auto");
-    if (want_kd && c->nnz > 0) {
-        // one 1024-thread workgroup per CU when dist fills the LDS; smaller graphs run several
-        // 256-thread workgroups (sources) per CU
-        int blk = n > 16384 ? 1024 : 256;
-        if (const char* e = getenv("SHD_ROUTE_KDBLOCK")) {
-            const int b = atoi(e);
-            if (b == 256 || b == 1024) blk = b;  // (512/768: the phase-A ring sizing assumes 256 or 1024)
-        }
-        int delta = 1;
-        if (const char* e = getenv("SHD_ROUTE_DELTA")) delta = std::max(1, atoi(e));
-        else {
-            // 1024-thread rows: the 15th percentile (38 on C4; seeded rows expand few vertices
-            // per bucket, so fewer, wider buckets pay: C4 57 -> 53 ms from the 6th percentile's
-            // 15.  Round-5 sweep, two reps each: 30/35/38-40/50/60 = 41.23-41.55/41.05/
-            // 41.04-41.40/41.90/42.92 ms).  256-thread rows (three compute waves) take the
-            // 22nd (55 on C3: 1.986 ms; 45/65/80 = 2.004-2.017/1.991/2.012-2.017 ms)
-            std::vector<int> ws(c->nnz);
-            for (int a = 0; a < c->nnz; a++) ws[a] = (int)w[a];
-            const size_t k = (size_t)c->nnz * (blk >= 1024 ? 15 : 22) / 100;
-            std::nth_element(ws.begin(), ws.begin() + k, ws.end());
-            delta = std::max(1, ws[k]);
-        }
-        const size_t base = kd_dispatch(blk, [&](auto B) { return kd_lds_bytes<decltype(B)::value>(n, 0); });
-        if (base + 2 * 512 <= kLdsBudget) {
-            // work queue: the rest of the CU's LDS at one workgroup per CU (large n), else
-            // enough for a few workgroups per CU
-            int qcap;
-            if (blk < 768) {
-                // four 256-thread workgroups per CU: the queue takes what is left of a quarter
-                const size_t quarter = kLdsBudget / 4;
-                qcap = base + 64 + 2 * 512 <= quarter ? (int)std::min<size_t>((size_t)n, (quarter - base - 64) / 2)
-                                                      : std::min(n, std::max(1024, n / 2));
-            } else qcap = (int)std::min<size_t>((size_t)n, (kLdsBudget - base - 64) / 2);
-            if (const char* e = getenv("SHD_ROUTE_QCAP")) qcap = std::min(qcap, std::max(64, atoi(e)));
-            // (a multiple of 8, and never 0: with fewer than 8 vertices the rounding left an
-            // empty queue, every vertex overflowed back to pending and the bucket loop spun)
-            qcap = std::max(8, qcap & ~7);
-            const size_t lds = kd_dispatch(blk, [&](auto B) { return kd_lds_bytes<decltype(B)::value>(n, qcap); });
-            int maxdeg = 0;
-            for (int v = 0; v < n; v++) maxdeg = std::max(maxdeg, row[v + 1] - row[v]);
-            // reliability table: every distinct 1-loss value (exact bits), indexed by u16
-            std::vector<double> rtab;
-            std::vector<uint16_t> ridx_out(c->nnz);
-            bool rtab_ok = true;
-            {
-                std::vector<std::pair<uint64_t, int>> keyed(c->nnz);
-                for (int a = 0; a < c->nnz; a++) {
-                    uint64_t bits;
-                    std::memcpy(&bits, &c->e_rel[eid[a]], 8);
-                    keyed[a] = {bits, a};
-                }
-                std::sort(keyed.begin(), keyed.end());
-                for (int q = 0; q < c->nnz && rtab_ok; q++) {
-                    if (q == 0 || keyed[q].first != keyed[q - 1].first) {
-                        double x;
-                        std::memcpy(&x, &keyed[q].first, 8);
-                        rtab.push_back(x);
-                        if (rtab.size() > 65535) rtab_ok = false;
-                    }
-                    ridx_out[keyed[q].second] = (uint16_t)(rtab.size() - 1);
-                }
-            }
-            if (lds <= kLdsBudget && maxdeg <= 65535 && rtab_ok) {
-                // out-arc records v | w << 16 (| ridx << 24 when packed); light in-CSR records
-                // {u | w << 16, ridx}, light = w < delta.  Fused parents (found during the
-                // expansion, 32-bit tie keys) need an undirected graph and packed records
-                // (w < 256, <= 256 reliabilities); otherwise the in-CSR holds every in-arc and
-                // phase B finds every parent.
-                std::vector<uint32_t> orec(c->nnz);
-                int maxw = 0;
-                for (int a = 0; a < c->nnz; a++) maxw = std::max(maxw, (int)w[a]);
-                bool packed = maxw < 256 && rtab.size() <= 256;
-                if (const char* e = getenv("SHD_ROUTE_KDPACK")) packed = packed && atoi(e) != 0;
-                for (int a = 0; a < c->nnz; a++)
-                    orec[a] = (uint32_t)col[a] | ((uint32_t)w[a] << 16) | (packed ? (uint32_t)ridx_out[a] << 24 : 0u);
-                c->kd_packed = packed ? 1 : 0;
-                const bool fused = !c->directed && packed;
-                c->kd_fused = fused ? 1 : 0;
-                std::vector<int> lrow(n + 1, 0);
-                std::vector<uint32_t> lrec;
-                for (int v = 0; v < n; v++) {
-                    for (int q = irow[v]; q < irow[v + 1]; q++) {
-                        const int a = order[q];
-                        if (fused && (int)w[a] >= delta) continue;
-                        lrec.push_back((uint32_t)cin[q] | ((uint32_t)w[a] << 16));
-                        lrec.push_back(ridx_out[a]);
-                    }
-                    lrow[v + 1] = (int)(lrec.size() / 2);
-                }
-                if (lrec.empty()) lrec.assign(2, 0u);
-                c->h_row = row; c->h_col = col; c->h_w = w; c->h_ridx = ridx_out;
-                rc = upload(c, &c->d_kd_lstart, lrow);
-                if (!rc) rc = upload(c, &c->d_kd_orec, orec);
-                if (!rc) rc = upload(c, &c->d_kd_oridx, ridx_out);
-                if (!rc) rc = upload(c, &c->d_kd_lrec, lrec);
-                if (!rc) rc = upload(c, &c->d_kd_rtab, rtab);
-                if (rc) return rc;
-                c->kd_nlight = lrow[n];
-                c->kd_nrtab = std::max<int>(1, (int)rtab.size());
-                for (int q = 0; q < (int)rtab.size(); q++)
-                    if (rtab[q] == 1.0) c->kd_rone = q;
-                // 16 waves per CU: 4 per SIMD at <= 128 VGPRs (amdgpu_waves_per_eu(4))
-                const int per_cu = std::max(1, std::min((int)(kLdsBudget / lds), 1024 / blk));
-                c->kd_slots = 256 * per_cu;
-                // tests cap the grid so that every workgroup runs many sources in turn
-                if (const char* e = getenv("SHD_ROUTE_KDGRID")) c->kd_slots = std::max(1, std::min(c->kd_slots, atoi(e)));
-                c->kd_stride = kd_ws_stride(n);
-                if (hipMalloc((void**)&c->d_kd_ws, c->kd_stride * (size_t)c->kd_slots) != hipSuccess)
-                    return SHD_ROUTE_ENOMEM;
-                c->allocs.push_back(c->d_kd_ws);
-                if (hipMalloc((void**)&c->d_kd_next, sizeof(int)) != hipSuccess) return SHD_ROUTE_ENOMEM;
-                c->allocs.push_back(c->d_kd_next);
-                if (hipMalloc((void**)&c->d_kd_stats, sizeof(unsigned long long) * 4) != hipSuccess ||
-                    hipMemset(c->d_kd_stats, 0, sizeof(unsigned long long) * 4) != hipSuccess)
-                    return SHD_ROUTE_ENOMEM;
-                c->allocs.push_back(c->d_kd_stats);
-                for (int pk = 0; pk < 2 && !rc; pk++) {
-                    const void* fn = kd_dispatch(blk, [&](auto B) {
-                        return pk ? (const void*)kd_plan_rows_kernel<decltype(B)::value>
-                                  : (const void*)sssp_delta_kernel<decltype(B)::value>;
-                    });
-                    rc = hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                }
-                if (rc) return rc;
-                c->kd = 1; c->kd_block = blk; c->kd_lds = lds; c->kd_delta = delta; c->kd_qcap = qcap;
-                if (blk < 1024 && !getenv("SHD_ROUTE_DELTA") && !getenv("SHD_ROUTE_QCAP")) {
-                    // hub rows in 1024-thread workgroups: that block's queue and bucket width
-                    const size_t hb = kd_lds_bytes<1024>(n, 0);
-                    if (hb + 2 * 512 <= kLdsBudget) {
-                        const int hq = std::max(8, (int)std::min<size_t>((size_t)n, (kLdsBudget - hb - 64) / 2) & ~7);
-                        const size_t hl = kd_lds_bytes<1024>(n, hq);
-                        std::vector<int> ws2(c->nnz);
-                        for (int a = 0; a < c->nnz; a++) ws2[a] = (int)w[a];
-                        const size_t k12 = (size_t)c->nnz * 12 / 100;
-                        std::nth_element(ws2.begin(), ws2.begin() + k12, ws2.end());
-                        if (hl <= kLdsBudget &&
-                            hipFuncSetAttribute((const void*)kd_plan_rows_kernel<1024>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)hl) == hipSuccess) {
-                            c->kd_hub_block = 1024; c->kd_hub_qcap = hq; c->kd_hub_lds = hl;
-                            // (the light in-CSR above holds the in-arcs with w < delta, and a
-                            // row's fused parents are exact only if its bucket width is at most
-                            // that: the hub rows' 12th percentile never exceeds the context's)
-                            c->kd_hub_delta = std::min(delta, std::max(1, ws2[k12]));
-                        }
-                    }
-                    if (const char* e = getenv("SHD_ROUTE_HUB1024")) if (atoi(e) == 0) c->kd_hub_block = 0;
-                }
-                c->kd_walk = kd_dispatch(blk, [&](auto B) { return kd_walk_fits<decltype(B)::value>(n, qcap, c->kd_nrtab); }) ? 1 : 0;
-                if (const char* e = getenv("SHD_ROUTE_KDWALK")) c->kd_walk = c->kd_walk && atoi(e) != 0;
-            }
+        if (s.kf.h) {
+            if (hipMalloc((void**)&c->d_kf_ws, s.kf.ws_stride * (size_t)s.kf.slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
+            c->allocs.push_back(c->d_kf_ws);
         }
     }
-    // KB batched kernel: segments of <= KB_SEG in-arcs, hub rows split
-    if (c->attr && want_kb) {
-        std::vector<KBSeg> segs;
-        std::vector<KBHub> hubs;
-        int npart = 0;
-        for (int v = 0; v < n; v++) {
-            const int a0 = irow[v], a1 = irow[v + 1];
-            if (a1 - a0 <= KB_SEG) { segs.push_back({v, a0, a1, -1}); continue; }
-            KBHub h{v, npart, 0, 0};
-            for (int a = a0; a < a1; a += KB_SEG) segs.push_back({v, a, std::min(a1, a + KB_SEG), npart++});
-            h.p1 = npart;
-            hubs.push_back(h);
-        }
-        // equal-length segments side by side: a wave's lanes finish their rows together
-        std::stable_sort(segs.begin(), segs.end(),
-                         [](const KBSeg& x, const KBSeg& y) { return (x.a1 - x.a0) > (y.a1 - y.a0); });
-        // thread t takes segments t, t + KB_BLOCK, ...: a sweep lasts as long as the wave
-        // whose lanes' longest segments add up most.  Each block of KB_BLOCK segments may
-        // run long->short or short->long over the threads; pick the directions with the
-        // smallest such wave time (C2: 29 -> 22 arc steps; the mean is 20)
-        {
-            const int nb = ((int)segs.size() + KB_BLOCK - 1) / KB_BLOCK;
-            constexpr int kWaves = KB_BLOCK / 64;
-            auto cost = [&](unsigned dirs) {
-                int wt[kWaves] = {0};
-                for (int b = 0; b < nb; b++) {
-                    const int k0 = b * KB_BLOCK, cnt = std::min((int)segs.size() - k0, KB_BLOCK);
-                    for (int w = 0; w < kWaves; w++) {
-                        int mx = 0;
-                        for (int l = w * 64; l < std::min(cnt, w * 64 + 64); l++) {
-                            const KBSeg& sg = segs[k0 + (((dirs >> b) & 1u) ? cnt - 1 - l : l)];
-                            mx = std::max(mx, sg.a1 - sg.a0);
-                        }
-                        wt[w] += mx;
-                    }
-                }
-                return *std::max_element(wt, wt + kWaves);
-            };
-            unsigned best = 0;
-            if (nb <= 12) {
-                int bc = cost(0);
-                for (unsigned d = 1; d < (1u << nb); d++) {
-                    const int c2 = cost(d);
-                    if (c2 < bc) { bc = c2; best = d; }
-                }
-            }
-            for (int b = 0; b < nb; b++)
-                if ((best >> b) & 1u) {
-                    const int k0 = b * KB_BLOCK, cnt = std::min((int)segs.size() - k0, KB_BLOCK);
-                    std::reverse(segs.begin() + k0, segs.begin() + k0 + cnt);
-                }
-        }
-        const KBLayout KL = KBLayout::make(n, c->nnz, npart);
-        const size_t kbl = kKBSmall + KL.total;
-        if (kbl <= kLdsBudget) {
-            rc = upload(c, &c->d_kb_seg, segs);
-            if (!rc && !hubs.empty()) rc = upload(c, &c->d_kb_hub, hubs);
-            if (!rc) rc = hip_check(hipFuncSetAttribute((const void*)sssp_batch_kernel,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kbl));
-            if (rc) return rc;
-            c->kb = 1; c->kb_lds = kbl; c->kb_nseg = (int)segs.size(); c->kb_nhub = (int)hubs.size();
-            c->kb_npart = npart;
-            // fused rows (no key rows, no K2): records u << 16 | ridx << 8 | w need w < 256 and
-            // <= 254 distinct reliabilities; parent records of <= KB_RIT segments per thread
-            int maxw = 0;
-            for (int a = 0; a < c->nnz; a++) maxw = std::max(maxw, (int)w[a]);
-            std::map<uint64_t, int> rix;
-            for (int q = 0; q < c->nnz; q++) {
-                uint64_t bits;
-                std::memcpy(&bits, &rin[q], 8);
-                rix.emplace(bits, 0);
-            }
-            // staged targets: as many as the rest of the LDS holds (one chunk when nt <= n)
-            const size_t fb0 = kKBSmall + KBLayout::make(n, c->nnz, npart, true, 0).total;
-            int tcap = fb0 < kLdsBudget ? (int)std::min<size_t>((size_t)n, (kLdsBudget - fb0 - 64) / 4) : 0;
-            tcap = tcap >= 64 ? (tcap & ~63) : 0;
-            const size_t fbl = kKBSmall + KBLayout::make(n, c->nnz, npart, true, tcap).total;
-            bool fuse = maxw < 256 && rix.size() <= (size_t)KB_ONE && (int)segs.size() <= KB_RIT * KB_BLOCK &&
-                        (int)hubs.size() <= KB_BLOCK && c->nnz < 0xFFFF && KB_SRC * n <= KB_CV * KB_BLOCK && npart < 0xFFFF && tcap >= 64 &&
-                        fbl <= kLdsBudget;
-            if (const char* e = getenv("SHD_ROUTE_KBTCAP")) tcap = std::max(64, std::min(tcap, atoi(e)) & ~63);
-            if (const char* e = getenv("SHD_ROUTE_KBFUSE")) fuse = fuse && atoi(e) != 0;
-            if (fuse) {
-                std::vector<double> rtab;
-                for (auto& kv : rix) {
-                    kv.second = (int)rtab.size();
-                    double x;
-                    std::memcpy(&x, &kv.first, 8);
-                    rtab.push_back(x);
-                }
-                std::vector<uint32_t> farc(((size_t)c->nnz + 3) / 4 * 4, 0u);
-                for (int q = 0; q < c->nnz; q++) {
-                    uint64_t bits;
-                    std::memcpy(&bits, &rin[q], 8);
-                    farc[q] = ((uint32_t)cin[q] << 16) | ((uint32_t)rix[bits] << 8) | (uint32_t)w[order[q]];
-                }
-                rc = upload(c, &c->d_kbf_arc, farc);
-                if (!rc) rc = upload(c, &c->d_kbf_rtab, rtab);
-                if (!rc) rc = hip_check(hipFuncSetAttribute((const void*)sssp_batch_rows_kernel,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbl));
-                if (rc) return rc;
-                c->kb_fused = 1; c->kbf_lds = fbl; c->kbf_nrtab = (int)rtab.size(); c->kbf_tcap = tcap;
-            }
-            // tests cap the grid so that every workgroup runs several batches in turn
-            if (const char* e = getenv("SHD_ROUTE_KBGRID")) c->kb_grid_cap = std::max(1, atoi(e));
-        }
-    }
-    c->sel = c->kb ? 2 : c->kd ? 4 : c->k32 ? 1 : 0;  // KB (C2-class), else KD (C3/C4-class)
+    // the staged copies have served, but for the planner's rtab index per arc
+    c->h_ridx = std::move(s.kd.oridx);
+    s.arrays([](const char*, auto& h, auto*&) { std::remove_reference_t<decltype(h)>().swap(h); });
+    s.inrows.order = {}; s.inrows.src_of = {};
+    c->sel = s.sel;
+    c->inrows = std::move(s.inrows); c->k32 = std::move(s.k32); c->attr = s.attr;
+    c->kb = std::move(s.kb); c->kd = std::move(s.kd); c->kf = std::move(s.kf);
     return SHD_ROUTE_OK;
 }
 
 DevDelta kd_args(const shd_route* c) {
     DevDelta k;
-    k.n = c->n; k.nw = (c->n + 63) / 64; k.bound = c->k32_bound; k.delta = c->kd_delta;
-    k.fused = c->kd_fused; k.rc = c->kd_qcap;
-    k.row = c->d_row; k.orec = c->d_kd_orec; k.oridx = c->d_kd_oridx;
-    k.nnz = c->nnz; k.lrow = c->d_kd_lstart; k.lrec = reinterpret_cast<const uint2*>(c->d_kd_lrec); k.nlight = c->kd_nlight;
-    k.rtab = c->d_kd_rtab; k.nrtab = c->kd_nrtab; k.rone = c->kd_rone; k.walk = c->kd_walk; k.packed = c->kd_packed;
+    k.n = c->n; k.nw = (c->n + 63) / 64; k.bound = c->k32.bound; k.delta = c->kd.delta;
+    k.fused = c->kd.fused; k.rc = c->kd.qcap;
+    k.row = c->d_row; k.orec = c->kd.d_orec; k.oridx = c->kd.d_oridx;
+    k.nnz = c->nnz; k.lrow = c->kd.d_lrow; k.lrec = reinterpret_cast<const uint2*>(c->kd.d_lrec); k.nlight = c->kd.nlight;
+    k.rtab = c->kd.d_rtab; k.nrtab = c->kd.nrtab; k.rone = c->kd.rone; k.walk = c->kd.walk; k.packed = c->kd.packed;
     k.vf = c->d_vf; k.self_w = c->d_self_w; k.self_r = c->d_self_r; k.dbg = c->d_dbg; k.dflags = 0;
     // a factor of exactly 1.0 multiplies as a no-op: KD reads vf only where one is not
     k.has_vf = c->vf_lossy;
@@ -716,19 +336,119 @@ int kd_launch(shd_route* c, DevDelta k, int* next, const int32_t* d_src, int ns,
     if (ns <= 0) return SHD_ROUTE_OK;
     k.next = next;
     if (!ws) ws = c->d_kd_ws;
-    const int grid = std::min(ns, max_grid > 0 ? std::min(max_grid, c->kd_slots) : c->kd_slots);
+    const int grid = std::min(ns, max_grid > 0 ? std::min(max_grid, c->kd.slots) : c->kd.slots);
     // (hub: the planner's rows in 1024-thread workgroups where the context's are smaller)
-    const bool big = hub && planner && c->kd_hub_block > 0;
-    size_t lds = c->kd_lds;
-    if (big) { k.rc = c->kd_hub_qcap; k.delta = c->kd_hub_delta; lds = c->kd_hub_lds; }
-    kd_dispatch(big ? c->kd_hub_block : c->kd_block, [&](auto B) {
+    const bool big = hub && planner && c->kd.hub_block > 0;
+    size_t lds = c->kd.lds;
+    if (big) { k.rc = c->kd.hub_qcap; k.delta = c->kd.hub_delta; lds = c->kd.hub_lds; }
+    kd_dispatch(big ? c->kd.hub_block : c->kd.block, [&](auto B) {
         constexpr int b = decltype(B)::value;
         if (planner)
             hipLaunchKernelGGL(kd_plan_rows_kernel<b>, dim3(grid), dim3(b), lds, st, k, d_src, ns, d_tgt,
-                               nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err, ws, c->kd_stride);
+                               nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err, ws, c->kd.stride);
         else
-            hipLaunchKernelGGL(sssp_delta_kernel<b>, dim3(grid), dim3(b), c->kd_lds, st, k, d_src, ns, d_tgt,
-                               nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err, ws, c->kd_stride);
+            hipLaunchKernelGGL(sssp_delta_kernel<b>, dim3(grid), dim3(b), c->kd.lds, st, k, d_src, ns, d_tgt,
+                               nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err, ws, c->kd.stride);
+        return 0;
+    });
+    return hip_check(hipGetLastError());
+}
+
+DevKB kb_args(const shd_route* c, int ns) {
+    DevKB kb;
+    kb.n = c->n; kb.nnz = c->nnz; kb.nseg = c->kb.nseg; kb.nhub = c->kb.nhub; kb.npart = c->kb.npart;
+    kb.bound = c->k32.bound; kb.arc = c->kb.fused ? c->kb.d_farc : c->kb.d_arc; kb.row_in = c->inrows.d_irow;
+    kb.seg = c->kb.d_seg; kb.hub = c->kb.d_hub;
+    kb.rtab = c->kb.d_rtab; kb.nrtab = c->kb.f_nrtab; kb.tcap = c->kb.f_tcap;
+    kb.vf = c->d_vf; kb.self_w = c->d_self_w; kb.self_r = c->d_self_r;
+    kb.dbg = c->d_dbg ? c->d_dbg + (size_t)ns * 8 : nullptr;
+    return kb;
+}
+
+DevAttr attr_args(const shd_route* c) {
+    DevAttr at;
+    at.n = c->n; at.row_in = c->inrows.d_irow; at.col_in = c->k32.d_col_in; at.r_in = c->k32.d_r_in;
+    at.vf = c->d_vf; at.self_w = c->d_self_w; at.self_r = c->d_self_r;
+    at.dbg = c->d_dbg;
+    return at;
+}
+
+DevK32 k32_args(const shd_route* c) {
+    DevK32 k;
+    k.n = c->n; k.bound = c->k32.bound; k.row = c->d_row; k.arc = c->k32.d_arc; k.row_in = c->inrows.d_irow;
+    k.col_in = c->k32.d_col_in; k.r_in = c->k32.d_r_in; k.vf = c->d_vf; k.self_w = c->d_self_w;
+    k.self_r = c->d_self_r;
+    k.dbg = c->d_dbg;
+    return k;
+}
+
+DevF64D kf_args(const shd_route* c) {
+    DevF64D k;
+    k.n = c->n; k.nw = (c->n + 63) / 64; k.delta = c->kf.delta;
+    k.row = c->d_row; k.col = c->d_col; k.w = c->d_w;
+    k.row_in = c->d_row_in; k.col_in = c->d_col_in; k.w_in = c->d_w_in;
+    k.rix_in = c->kf.d_rix; k.rtab = c->kf.d_rtab; k.nrtab = c->kf.nrtab;
+    k.hring = 0;
+    if (const char* e = getenv("SHD_ROUTE_KFH_RING")) k.hring = std::max(0, atoi(e));  // (tests: a small ring)
+    k.vf = c->d_vf; k.self_w = c->d_self_w; k.self_r = c->d_self_r; k.dbg = c->d_dbg;
+    k.opk = c->kf.d_opk; k.ipk = c->kf.d_ipk; k.wscale = c->kf.wscale;
+    return k;
+}
+
+// the rows of ns sources by KB: the fused kernel, or distances and parents for KB_SRC sources
+// per workgroup -> key rows -> K2
+int kb_launch(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, int64_t ld, double* d_lat,
+              double* d_rel, double* d_row_min, hipStream_t st) {
+    const DevKB kb = kb_args(c, ns);
+    int gridb = std::min((ns + KB_SRC - 1) / KB_SRC, 1 << 20);
+    if (c->kb.grid_cap > 0) gridb = std::min(gridb, c->kb.grid_cap);
+    if (c->kb.fused) {
+        hipLaunchKernelGGL(sssp_batch_rows_kernel, dim3(gridb), dim3(KB_BLOCK), c->kb.f_lds, st, kb, d_src, ns,
+                           c->d_err, d_tgt, nt, (long long)ld, d_lat, d_rel, d_row_min);
+        return hip_check(hipGetLastError());
+    }
+    const size_t need = (size_t)ns * c->n;
+    if (need > c->keys_cap) {
+        if (c->d_keys) (void)hipFree(c->d_keys);
+        c->d_keys = nullptr;
+        c->keys_cap = 0;
+        if (hipMalloc((void**)&c->d_keys, need * sizeof(uint32_t)) != hipSuccess) return SHD_ROUTE_ENOMEM;
+        c->keys_cap = need;
+    }
+    hipLaunchKernelGGL(sssp_batch_kernel, dim3(gridb), dim3(KB_BLOCK), c->kb.lds, st, kb, d_src, ns,
+                       c->d_keys, (long long)c->n, c->d_err);
+    int rc = hip_check(hipGetLastError());
+    if (rc) return rc;
+    const int grida = std::min(ns, 1 << 20);
+    hipLaunchKernelGGL(path_attr_kernel<256>, dim3(grida), dim3(256), c->attr.lds, st, attr_args(c), c->d_keys,
+                       (long long)c->n, d_src, ns, d_tgt, nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
+    return hip_check(hipGetLastError());
+}
+
+int k32_launch(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, int64_t ld, double* d_lat,
+               double* d_rel, double* d_row_min, hipStream_t st) {
+    const DevK32 k = k32_args(c);
+    const int grid = std::min(ns, 1 << 20);
+    k32_dispatch(c->k32.block, [&](auto B) {
+        constexpr int b = decltype(B)::value;
+        hipLaunchKernelGGL(sssp_k32_kernel<b>, dim3(grid), dim3(b), c->k32.lds, st, k, d_src, ns, d_tgt, nt,
+                           (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
+        return 0;
+    });
+    return hip_check(hipGetLastError());
+}
+
+int kf_launch(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, int64_t ld, double* d_lat,
+              double* d_rel, double* d_row_min, hipStream_t st) {
+    const DevF64D k = kf_args(c);
+    const int grid = std::min(ns, c->kf.slots);
+    // (KFH's slices: one per workgroup slot, grid <= kf.slots)
+    kf_dispatch(c->kf.block, c->kf.h, c->kf.d_opk != nullptr, [&](auto B, auto H, auto P) {
+        constexpr int b = decltype(B)::value;
+        constexpr bool h = decltype(H)::value;
+        hipLaunchKernelGGL((sssp_f64d_kernel<b, h, decltype(P)::value>), dim3(grid), dim3(b), c->kf.lds, st, k, d_src,
+                           ns, d_tgt, nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err, h ? c->d_kf_ws : (char*)nullptr,
+                           h ? c->kf.ws_stride : (size_t)0);
         return 0;
     });
     return hip_check(hipGetLastError());
@@ -761,110 +481,6 @@ const char* shd_route_strerror(int code) {
     }
 }
 
-// KF eligibility + device arrays (graphs the integer kernels do not take): per in-arc index
-// of its 1 - loss in a table of the distinct values, bucket width, block size.  Fits when
-// the per-source LDS state does and every thread holds at most 16 vertices in the level
-// passes (n <= 16 B); above that KFH (n <= 65535: the ring is u16), one 1024-thread
-// workgroup per CU with its vertex state in an HBM slice (C4f: 550 KB per slice).
-int prepare_kf(shd_route* c, const std::vector<int>& col, const std::vector<double>& w, const std::vector<int>& row_in,
-               const std::vector<int>& col_in, const std::vector<double>& w_in, const std::vector<double>& r_in) {
-    const int n = c->n;
-    const char* force = getenv("SHD_ROUTE_KERNEL");
-    if (force && *force && strcmp(force, "kf") && strcmp(force, "auto")) return SHD_ROUTE_OK;
-    if (c->nnz == 0 || n > 65535) return SHD_ROUTE_OK;
-    std::vector<double> rtab;
-    std::vector<uint8_t> rix(c->nnz);
-    {
-        std::vector<std::pair<uint64_t, int>> keyed(c->nnz);
-        for (int a = 0; a < c->nnz; a++) {
-            uint64_t bits;
-            std::memcpy(&bits, &r_in[a], 8);
-            keyed[a] = {bits, a};
-        }
-        std::sort(keyed.begin(), keyed.end());
-        for (int q = 0; q < c->nnz; q++) {
-            if (q == 0 || keyed[q].first != keyed[q - 1].first) {
-                if ((int)rtab.size() == 254) return SHD_ROUTE_OK;  // (255 marks unreachable)
-                double x;
-                std::memcpy(&x, &keyed[q].first, 8);
-                rtab.push_back(x);
-            }
-            rix[keyed[q].second] = (uint8_t)(rtab.size() - 1);
-        }
-    }
-    int blk = 0;
-    size_t lds = 0;
-    bool hbm = false;
-    if (n <= 16 * 256 && kf_lds_bytes<256>(n) <= kLdsBudget / 4) { blk = 256; lds = kf_lds_bytes<256>(n); }
-    else if (n <= 16 * 1024 && kf_lds_bytes<1024>(n) <= kLdsBudget) { blk = 1024; lds = kf_lds_bytes<1024>(n); }
-    else if (n <= 64 * 1024 && kfh_lds_bytes<1024>(n) <= kLdsBudget) { blk = 1024; lds = kfh_lds_bytes<1024>(n); hbm = true; }
-    if (const char* e = getenv("SHD_ROUTE_KFH"))  // (tests: KFH on graphs KF takes)
-        if (atoi(e) && n <= 64 * 1024 && kfh_lds_bytes<1024>(n) <= kLdsBudget) { blk = 1024; lds = kfh_lds_bytes<1024>(n); hbm = true; }
-    if (!blk) return SHD_ROUTE_OK;
-    // bucket width: the 40th percentile of arc latencies (KF rounds cost far more than the
-    // re-expansions wider buckets bring: C3f 15.0 / 13.4 / 13.1 ms at the 12th / 25th / 50th,
-    // C2f 0.60 / 0.55 / 0.57 ms); KFH the 10th, where a re-expansion is HBM traffic (C4f, the
-    // width in ms: 15 / 25 / 35 / 50 / 70 / ~100 (40th) / 200: 822 / 815 / 822 / 835 / 842 /
-    // 886 / 1061 ms)
-    std::vector<double> ws(w_in.begin(), w_in.end());
-    const size_t k = ws.size() * (hbm ? 10 : 40) / 100;
-    std::nth_element(ws.begin(), ws.begin() + k, ws.end());
-    double delta = ws[k];
-    if (const char* e = getenv("SHD_ROUTE_KFDELTA")) delta = atof(e);
-    if (!(delta > 0.0) || std::isinf(delta)) delta = c->min_w > 0 ? c->min_w : 1.0;
-    int rc = upload(c, &c->d_kf_rix, rix);
-    if (!rc) rc = upload(c, &c->d_kf_rtab, rtab);
-    // Packed arcs (KFH): when every latency is a decimal k / scale (scale 1, 10, 100 or 1000)
-    // with k < 65536, an arc is one u32, head | k << 16, and the kernel divides k by the scale
-    // -- IEEE division of two exact integers is the correctly rounded k / scale, the double the
-    // decimal parses to, and each arc is checked here (C4f's latencies have two decimals: 4
-    // bytes per arc read instead of 12; C4f 780 -> 764 ms).  The LDS kernels keep f64 arcs:
-    // there the division costs more than the bytes (C3f 10.39 -> 10.59, C2f 0.45 -> 0.49 ms)
-    double wscale = 0.0;
-    if (hbm && !(getenv("SHD_ROUTE_KFPK") && atoi(getenv("SHD_ROUTE_KFPK")) == 0)) {
-        for (const double sc : {1.0, 10.0, 100.0, 1000.0}) {
-            auto fits = [&](const std::vector<double>& ws) {
-                for (const double x : ws) {
-                    const double k = std::nearbyint(x * sc);
-                    if (!(k >= 1.0 && k <= 65535.0) || k / sc != x) return false;
-                }
-                return true;
-            };
-            if (fits(w) && (c->directed ? fits(w_in) : true)) { wscale = sc; break; }
-        }
-    }
-    if (!rc && wscale > 0.0) {
-        auto pack = [&](const std::vector<int>& cc, const std::vector<double>& ws) {
-            std::vector<uint32_t> pk(cc.size());
-            for (size_t a = 0; a < cc.size(); a++)
-                pk[a] = (uint32_t)cc[a] | ((uint32_t)std::nearbyint(ws[a] * wscale) << 16);
-            return pk;
-        };
-        rc = upload(c, &c->d_kf_opk, pack(col, w));
-        if (!rc) {
-            if (c->directed) rc = upload(c, &c->d_kf_ipk, pack(col_in, w_in));
-            else c->d_kf_ipk = c->d_kf_opk;
-        }
-        c->kf_wscale = wscale;
-    }
-    const bool pk = wscale > 0.0;
-    const void* kfn = hbm ? (pk ? (const void*)sssp_f64d_kernel<1024, true, true> : (const void*)sssp_f64d_kernel<1024, true>)
-                    : blk == 256 ? (pk ? (const void*)sssp_f64d_kernel<256, false, true> : (const void*)sssp_f64d_kernel<256>)
-                                 : (pk ? (const void*)sssp_f64d_kernel<1024, false, true> : (const void*)sssp_f64d_kernel<1024>);
-    if (!rc) rc = hip_check(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (rc) return rc;
-    c->kf_block = blk; c->kf_lds = lds; c->kf_delta = delta; c->kf_nrtab = (int)rtab.size();
-    c->kf_slots = 256 * std::max(1, std::min((int)(kLdsBudget / lds), 1024 / blk));
-    if (hbm) {
-        c->kf_h = 1;
-        c->kf_ws_stride = kfh_ws_stride<1024>(n);
-        if (hipMalloc((void**)&c->d_kf_ws, c->kf_ws_stride * (size_t)c->kf_slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
-        c->allocs.push_back(c->d_kf_ws);
-    }
-    c->sel = 5;
-    return SHD_ROUTE_OK;
-}
-
 int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
     if (!out || !g) return SHD_ROUTE_EINVAL;
     *out = nullptr;
@@ -894,48 +510,12 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
     c->e_src.assign(g->edge_src, g->edge_src + m);
     c->e_dst.assign(g->edge_dst, g->edge_dst + m);
     c->e_lat.assign(g->edge_latency, g->edge_latency + m);
-    c->e_rel.resize(m);
-    for (int e = 0; e < m; e++) c->e_rel[e] = (1.0f - g->edge_packetloss[e]);  // topology.c:437
-
-    // arcs for SSSP (self-loops excluded: w > 0 never relaxes them)
-    std::vector<int32_t> ar, ac, ae, ir, ic, ie;
-    std::vector<double> self_w(n, NAN), self_r(n, NAN);
-    std::vector<int> loops(n, 0), degm(n, 0);
-    double maxw = 0;
-    c->min_w = m ? INFINITY : 0;
-    bool integral = true;
-    for (int e = 0; e < m; e++) {
-        int a = g->edge_src[e], b = g->edge_dst[e];
-        double w = g->edge_latency[e];
-        maxw = std::max(maxw, w);
-        c->min_w = std::min(c->min_w, w);
-        if (w != std::floor(w) || w > 1048576.0) integral = false;
-        if (a == b) {
-            if (std::isnan(self_w[a])) { self_w[a] = w; self_r[a] = c->e_rel[e]; }
-            loops[a]++;
-            continue;
-        }
-        ar.push_back(a); ac.push_back(b); ae.push_back(e);
-        degm[a]++;
-        if (!c->directed) { ar.push_back(b); ac.push_back(a); ae.push_back(e); degm[b]++; }
-        else { ir.push_back(b); ic.push_back(a); ie.push_back(e); }
-    }
-    c->integer_w = integral && (double)n * maxw < 2147483647.0;
-    c->max_w = maxw;
-    for (int v = 0; v < n; v++)
-        if (!std::isnan(self_w[v]) && !(self_w[v] == std::floor(self_w[v]) && self_w[v] < 65535.0)) c->self16 = 0;
-    std::vector<int> row, col, row_in, col_in, eid;
-    std::vector<double> w, r, w_in, r_in;
-    build_csr(n, ar, ac, ae, c->e_lat, c->e_rel, row, col, w, r, &eid);
-    if (c->directed) build_csr(n, ir, ic, ie, c->e_lat, c->e_rel, row_in, col_in, w_in, r_in);
-    c->nnz = (int)col.size();
-    for (int v = 0; v < n && !c->multigraph; v++)
-        for (int a = row[v] + 1; a < row[v + 1]; a++)
-            if (col[a] == col[a - 1]) { c->multigraph = 1; break; }
-    for (int v = 0; v < n; v++) if (loops[v] > 1) c->multigraph = 1;
+    HostGraph h = HostGraph::make(g);
+    c->nnz = h.nnz; c->integer_w = h.integer_w; c->multigraph = h.multigraph; c->self16 = h.self16;
+    c->min_w = h.min_w; c->max_w = h.max_w;
 
     // topology.c:738-806: strongly connected, one cluster
-    if (!strongly_connected(n, row, col, c->directed ? row_in : row, c->directed ? col_in : col)) {
+    if (!strongly_connected(n, h.row, h.col, h.in_row(), h.in_col())) {
         delete c;
         return SHD_ROUTE_EINVAL;
     }
@@ -943,8 +523,8 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
     c->complete = 1;
     for (int v = 0; v < n; v++) {
         long long ecount;
-        if (c->directed) ecount = (row[v + 1] - row[v]) + loops[v];
-        else ecount = (row[v + 1] - row[v]) + 2LL * loops[v] - (loops[v] > 0 ? 1 : 0);
+        if (c->directed) ecount = (h.row[v + 1] - h.row[v]) + h.loops[v];
+        else ecount = (h.row[v + 1] - h.row[v]) + 2LL * h.loops[v] - (h.loops[v] > 0 ? 1 : 0);
         if (ecount < n) { c->complete = 0; break; }
     }
 
@@ -958,21 +538,21 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
             }
 
     int rc = SHD_ROUTE_OK;
-    if (!rc) rc = upload(c, &c->d_row, row);
-    if (!rc) rc = upload(c, &c->d_col, col);
-    if (!rc) rc = upload(c, &c->d_w, w);
-    if (!rc) rc = upload(c, &c->d_r, r);
+    if (!rc) rc = upload(c, &c->d_row, h.row);
+    if (!rc) rc = upload(c, &c->d_col, h.col);
+    if (!rc) rc = upload(c, &c->d_w, h.w);
+    if (!rc) rc = upload(c, &c->d_r, h.r);
     if (c->directed) {
-        if (!rc) rc = upload(c, &c->d_row_in, row_in);
-        if (!rc) rc = upload(c, &c->d_col_in, col_in);
-        if (!rc) rc = upload(c, &c->d_w_in, w_in);
-        if (!rc) rc = upload(c, &c->d_r_in, r_in);
+        if (!rc) rc = upload(c, &c->d_row_in, h.row_in);
+        if (!rc) rc = upload(c, &c->d_col_in, h.col_in);
+        if (!rc) rc = upload(c, &c->d_w_in, h.w_in);
+        if (!rc) rc = upload(c, &c->d_r_in, h.r_in);
     } else {
         c->d_row_in = c->d_row; c->d_col_in = c->d_col; c->d_w_in = c->d_w; c->d_r_in = c->d_r;
     }
     if (!rc) rc = upload(c, &c->d_vf, vf);
-    if (!rc) rc = upload(c, &c->d_self_w, self_w);
-    if (!rc) rc = upload(c, &c->d_self_r, self_r);
+    if (!rc) rc = upload(c, &c->d_self_w, h.self_w);
+    if (!rc) rc = upload(c, &c->d_self_r, h.self_r);
     if (!rc) {
         std::vector<int> z(1, 0);
         rc = upload(c, &c->d_err, z);
@@ -988,16 +568,16 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
             rc = alloc_ws(c);
         }
     }
-    if (!rc) rc = prepare_k32(c, row, col, w, eid, c->directed ? row_in : row, c->directed ? col_in : col,
-                              c->directed ? w_in : w);
-    if (!rc && c->sel == 0)
-        rc = prepare_kf(c, col, w, c->directed ? row_in : row, c->directed ? col_in : col, c->directed ? w_in : w,
-                        c->directed ? r_in : r);
+    if (!rc) rc = apply_selection(c, select_all(SelectInput(h), SelectKnobs::from_env()));
     if (rc) {
         shd_route_destroy(c);
         return rc;
     }
-    if (c->sel == 4 && c->kd_fused) host_pool();  // the planner's workers, parked until a plan
+    c->e_rel = std::move(h.e_rel);
+    if (c->kd.ok) {  // the planner's host copies
+        c->h_row = std::move(h.row); c->h_col = std::move(h.col); c->h_w = std::move(h.w);
+    }
+    if (c->sel == 4 && c->kd.fused) host_pool();  // the planner's workers, parked until a plan
     *out = c;
     return SHD_ROUTE_OK;
 }
@@ -1020,7 +600,7 @@ void shd_route_destroy(shd_route_t* c) {
 // u16 latency payloads are exact: integer latencies whose shortest paths are proven below
 // 0xFFFF and integer self-loops (the diagonal, kept out of the CSR and its bound) below it
 static bool lat16_ok(const shd_route* c) {
-    return c->integer_w && c->self16 && c->k32_bound > 0 && c->k32_bound < 0xFFFF;
+    return c->integer_w && c->self16 && c->k32.bound > 0 && c->k32.bound < 0xFFFF;
 }
 
 int shd_route_get_info(const shd_route_t* c, shd_route_info_t* info) {
@@ -1034,12 +614,12 @@ int shd_route_get_info(const shd_route_t* c, shd_route_info_t* info) {
     info->integer_weights = c->integer_w;
     info->multigraph = c->multigraph;
     info->device = c->device;
-    info->lds_resident = ((c->lds || c->sel) && !c->kf_h) ? 1 : 0;  // (KFH: vertex state in HBM)
+    info->lds_resident = ((c->lds || c->sel) && !c->kf.h) ? 1 : 0;  // (KFH: vertex state in HBM)
     info->kernel = c->sel;
-    info->dist_bound = c->k32_bound;
-    info->block = c->sel == 2 ? KB_BLOCK : c->sel == 3 ? 1024 : c->sel == 4 ? c->kd_block
-                : c->sel == 1 ? c->k32_block : c->sel == 5 ? c->kf_block : kBlock;
-    info->reserved = c->sel == 4 ? c->kd_delta : c->sel == 2 ? c->kb_fused : c->sel == 5 ? (int)c->kf_wscale : 0;
+    info->dist_bound = c->k32.bound;
+    info->block = c->sel == 2 ? KB_BLOCK : c->sel == 3 ? 1024 : c->sel == 4 ? c->kd.block
+                : c->sel == 1 ? c->k32.block : c->sel == 5 ? c->kf.block : kBlock;
+    info->reserved = c->sel == 4 ? c->kd.delta : c->sel == 2 ? c->kb.fused : c->sel == 5 ? (int)c->kf.wscale : 0;
     info->lat16 = lat16_ok(c) ? 1 : 0;
     info->device_bytes = c->device_bytes;
     info->min_edge_latency = c->min_w;
@@ -1062,97 +642,15 @@ int shd_route_rows_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const
         return hip_check(hipGetLastError());
     }
     const int dispatch = (flags & SHD_ROUTE_DISPATCH) ? 1 : 0;
-    if (c->sel == 2 && !(dispatch && c->prefer_direct)) {
-        DevKB kb;
-        kb.n = c->n; kb.nnz = c->nnz; kb.nseg = c->kb_nseg; kb.nhub = c->kb_nhub; kb.npart = c->kb_npart;
-        kb.bound = c->k32_bound; kb.arc = c->d_kb_arc; kb.row_in = c->d_k32_row_in; kb.seg = c->d_kb_seg;
-        kb.hub = c->d_kb_hub;
-        kb.rtab = c->d_kbf_rtab; kb.nrtab = c->kbf_nrtab;
-        kb.vf = c->d_vf; kb.self_w = c->d_self_w; kb.self_r = c->d_self_r;
-        int gridb = std::min((ns + KB_SRC - 1) / KB_SRC, 1 << 20);
-        if (c->kb_grid_cap > 0) gridb = std::min(gridb, c->kb_grid_cap);
-        if (c->kb_fused) {
-            // KB with fused path attributes: the rows in one kernel
-            kb.arc = c->d_kbf_arc;
-            kb.dbg = c->d_dbg ? c->d_dbg + (size_t)ns * 8 : nullptr;
-            kb.tcap = c->kbf_tcap;
-            hipLaunchKernelGGL(sssp_batch_rows_kernel, dim3(gridb), dim3(KB_BLOCK), c->kbf_lds, st, kb, d_src, ns,
-                               c->d_err, d_tgt, nt, (long long)ld, d_lat, d_rel, d_row_min);
-            return hip_check(hipGetLastError());
+    if (c->sel && !(dispatch && c->prefer_direct)) {
+        switch (c->sel) {
+            case 2: return kb_launch(c, d_src, ns, d_tgt, nt, ld, d_lat, d_rel, d_row_min, st);
+            case 4:
+                if (hipMemsetAsync(c->d_kd_next, 0, sizeof(int), st) != hipSuccess) return SHD_ROUTE_EDEVICE;
+                return kd_launch(c, kd_args(c), c->d_kd_next, d_src, ns, d_tgt, nt, ld, d_lat, d_rel, d_row_min, st);
+            case 1: return k32_launch(c, d_src, ns, d_tgt, nt, ld, d_lat, d_rel, d_row_min, st);
+            case 5: return kf_launch(c, d_src, ns, d_tgt, nt, ld, d_lat, d_rel, d_row_min, st);
         }
-        // KB distances+parents for KB_SRC sources per workgroup -> key rows -> K2
-        const size_t need = (size_t)ns * c->n;
-        if (need > c->keys_cap) {
-            if (c->d_keys) (void)hipFree(c->d_keys);
-            c->d_keys = nullptr;
-            c->keys_cap = 0;
-            if (hipMalloc((void**)&c->d_keys, need * sizeof(uint32_t)) != hipSuccess) return SHD_ROUTE_ENOMEM;
-            c->keys_cap = need;
-        }
-        kb.dbg = c->d_dbg ? c->d_dbg + (size_t)ns * 8 : nullptr;
-        hipLaunchKernelGGL(sssp_batch_kernel, dim3(gridb), dim3(KB_BLOCK), c->kb_lds, st, kb, d_src, ns,
-                           c->d_keys, (long long)c->n, c->d_err);
-        int rc = hip_check(hipGetLastError());
-        if (rc) return rc;
-        DevAttr at;
-        at.n = c->n; at.row_in = c->d_k32_row_in; at.col_in = c->d_k32_col_in; at.r_in = c->d_k32_r_in;
-        at.vf = c->d_vf; at.self_w = c->d_self_w; at.self_r = c->d_self_r;
-        at.dbg = c->d_dbg;
-        const int grida = std::min(ns, 1 << 20);
-        hipLaunchKernelGGL(path_attr_kernel<256>, dim3(grida), dim3(256), c->attr_lds, st, at, c->d_keys,
-                           (long long)c->n, d_src, ns, d_tgt, nt, (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    if (c->sel == 4 && !(dispatch && c->prefer_direct)) {
-        DevDelta k = kd_args(c);
-        if (hipMemsetAsync(c->d_kd_next, 0, sizeof(int), st) != hipSuccess) return SHD_ROUTE_EDEVICE;
-        return kd_launch(c, k, c->d_kd_next, d_src, ns, d_tgt, nt, ld, d_lat, d_rel, d_row_min, st);
-    }
-    if (c->sel == 1 && !(dispatch && c->prefer_direct)) {
-        DevK32 k;
-        k.n = c->n; k.bound = c->k32_bound; k.row = c->d_row; k.arc = c->d_arc; k.row_in = c->d_k32_row_in;
-        k.col_in = c->d_k32_col_in; k.r_in = c->d_k32_r_in; k.vf = c->d_vf; k.self_w = c->d_self_w;
-        k.self_r = c->d_self_r;
-        k.dbg = c->d_dbg;
-        const int grid = std::min(ns, 1 << 20);
-        if (c->k32_block == 256)
-            hipLaunchKernelGGL(sssp_k32_kernel<256>, dim3(grid), dim3(256), c->k32_lds, st, k, d_src, ns, d_tgt, nt,
-                               (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
-        else if (c->k32_block == 512)
-            hipLaunchKernelGGL(sssp_k32_kernel<512>, dim3(grid), dim3(512), c->k32_lds, st, k, d_src, ns, d_tgt, nt,
-                               (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
-        else
-            hipLaunchKernelGGL(sssp_k32_kernel<1024>, dim3(grid), dim3(1024), c->k32_lds, st, k, d_src, ns, d_tgt, nt,
-                               (long long)ld, d_lat, d_rel, d_row_min, c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    if (c->sel == 5 && !(dispatch && c->prefer_direct)) {
-        DevF64D k;
-        k.n = c->n; k.nw = (c->n + 63) / 64; k.delta = c->kf_delta;
-        k.row = c->d_row; k.col = c->d_col; k.w = c->d_w;
-        k.row_in = c->d_row_in; k.col_in = c->d_col_in; k.w_in = c->d_w_in;
-        k.rix_in = c->d_kf_rix; k.rtab = c->d_kf_rtab; k.nrtab = c->kf_nrtab;
-        k.hring = 0;
-        if (const char* e = getenv("SHD_ROUTE_KFH_RING")) k.hring = std::max(0, atoi(e));  // (tests: a small ring)
-        k.vf = c->d_vf; k.self_w = c->d_self_w; k.self_r = c->d_self_r; k.dbg = c->d_dbg;
-        k.opk = c->d_kf_opk; k.ipk = c->d_kf_ipk; k.wscale = c->kf_wscale;
-        const int grid = std::min(ns, c->kf_slots);
-        auto go = [&](auto kern, int blk, char* ws, size_t wst) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(blk), c->kf_lds, st, k, d_src, ns, d_tgt, nt, (long long)ld, d_lat,
-                               d_rel, d_row_min, c->d_err, ws, wst);
-        };
-        const bool pk = c->d_kf_opk != nullptr;
-        if (c->kf_h) {  // (the slices: one per workgroup slot, grid <= kf_slots)
-            if (pk) go(sssp_f64d_kernel<1024, true, true>, 1024, c->d_kf_ws, c->kf_ws_stride);
-            else go(sssp_f64d_kernel<1024, true>, 1024, c->d_kf_ws, c->kf_ws_stride);
-        } else if (c->kf_block == 256) {
-            if (pk) go(sssp_f64d_kernel<256, false, true>, 256, (char*)nullptr, (size_t)0);
-            else go(sssp_f64d_kernel<256>, 256, (char*)nullptr, (size_t)0);
-        } else {
-            if (pk) go(sssp_f64d_kernel<1024, false, true>, 1024, (char*)nullptr, (size_t)0);
-            else go(sssp_f64d_kernel<1024>, 1024, (char*)nullptr, (size_t)0);
-        }
-        return hip_check(hipGetLastError());
     }
     DevGraph g = dev_graph(c);
     if (c->lds) {
@@ -1235,7 +733,7 @@ int shd_route_rows(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t
     // many KD rows (at least one per resident workgroup slot, so the plan's landmark rows,
     // row store and table pay off): one seeded plan over all of them when the whole table
     // fits the device; small batches and any device allocation failure take the chunked rows
-    if (c && c->sel == 4 && c->kd_fused && ns >= 2 && ns >= c->kd_slots && nt >= 1 && src && tgt &&
+    if (c && c->sel == 4 && c->kd.fused && ns >= 2 && ns >= c->kd.slots && nt >= 1 && src && tgt &&
         !((flags & SHD_ROUTE_DISPATCH) && (c->complete || c->prefer_direct))) {
         const int rc = planned_host_rows(c, src, ns, tgt, nt, flags, lat_out, rel_out, row_min_out);
         if (rc != SHD_ROUTE_EUNSUPPORTED) return rc;
@@ -1328,9 +826,9 @@ constexpr int kFwMaxN = 12000;  // fw_rows keeps rel f64 + order u16 per vertex 
 // enqueued on the caller's stream, ahead of the table launches that follow it there.
 int fw_prepare(shd_route* c, hipStream_t st) {
     if (c->d_fwD) return SHD_ROUTE_OK;
-    if (!c->integer_w || c->multigraph || c->n > kFwMaxN || c->k32_bound <= 0 || c->k32_bound >= 0xFFFF)
+    if (!c->integer_w || c->multigraph || c->n > kFwMaxN || c->k32.bound <= 0 || c->k32.bound >= 0xFFFF)
         return SHD_ROUTE_EUNSUPPORTED;
-    const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32_bound + 2));
+    const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32.bound + 2));
     if (lds > kLdsBudget) return SHD_ROUTE_EUNSUPPORTED;
     const int np = (c->n + FW_T - 1) / FW_T * FW_T;
     int sp = 1;
@@ -1524,10 +1022,10 @@ int shd_route_fw_rows_async(shd_route_t* c, const int32_t* d_src, int32_t ns, co
                            c->d_fwpos, c->n, np, d_src, ns, c->d_fwkey);
     FWRowsArgs a;
     a.pk = c->fw_pk;
-    a.n = c->n; a.np = np; a.bound = c->k32_bound; a.D = c->d_fwD; a.key = c->d_fwkey; a.R = c->d_R;
+    a.n = c->n; a.np = np; a.bound = c->k32.bound; a.D = c->d_fwD; a.key = c->d_fwkey; a.R = c->d_R;
     a.rix = c->d_fwrix; a.rtab = c->d_fwrtab; a.nrtab = c->d_fwrix ? c->fw_nrtab : 0;
     a.vf = c->d_vf; a.self_w = c->d_self_w; a.self_r = c->d_self_r;
-    const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32_bound + 2));
+    const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32.bound + 2));
     // (512-thread workgroups since the u16 order list: C5 rows 0.92 -> 0.81 ms against 1024,
     // 0.86 at 256; SHD_ROUTE_FWRBLK=1024 / 256 for the A/B)
     int rblk = 512;

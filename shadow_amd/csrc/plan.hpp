@@ -530,10 +530,10 @@ struct PlanOptions {
     bool debug = false;
 
     int roots(const shd_route* c, int nj) const {
-        return seed_roots >= 0 ? seed_roots : lm_all && nland > 0 ? nj : c->kd_slots;
+        return seed_roots >= 0 ? seed_roots : lm_all && nland > 0 ? nj : c->kd.slots;
     }
     int depth(const shd_route* c, int nj) const {
-        return seed_depth > 0 ? seed_depth : std::max(8, nj / std::max(1, 2 * c->kd_slots));
+        return seed_depth > 0 ? seed_depth : std::max(8, nj / std::max(1, 2 * c->kd.slots));
     }
 };
 
@@ -542,16 +542,16 @@ PlanOptions plan_options(const shd_route* c, int ns, int world) {
     const int n = c->n;
     auto off = [](const char* k) { const char* e = getenv(k); return e && atoi(e) == 0; };
     o.seed = !off("SHD_ROUTE_SEED");
-    o.delta = c->kd_delta;
-    if (const char* e = getenv("SHD_ROUTE_PLAN_DELTA")) o.delta = std::max(1, std::min(c->kd_delta, atoi(e)));
+    o.delta = c->kd.delta;
+    if (const char* e = getenv("SHD_ROUTE_PLAN_DELTA")) o.delta = std::max(1, std::min(c->kd.delta, atoi(e)));
     double lmall_rps = PLAN_LMALL_RPS;
     if (const char* e = getenv("SHD_ROUTE_LMALL")) lmall_rps = atof(e);
     int lmall_small = 1;
     if (const char* e = getenv("SHD_ROUTE_LMALL_SMALL")) lmall_small = atoi(e);
-    o.lm_all = !c->multigraph && c->kd_slots > 0 &&
-               ((lmall_small && c->kd_block < 1024 && n >= 2048) ||
-                (double)ns / world <= lmall_rps * (double)c->kd_slots);
-    o.nland = c->multigraph ? 0 : std::min(c->kd_block >= 1024 ? 16 : 64, n);
+    o.lm_all = !c->multigraph && c->kd.slots > 0 &&
+               ((lmall_small && c->kd.block < 1024 && n >= 2048) ||
+                (double)ns / world <= lmall_rps * (double)c->kd.slots);
+    o.nland = c->multigraph ? 0 : std::min(c->kd.block >= 1024 ? 16 : 64, n);
     if (o.lm_all) o.nland = std::min(n, PLAN_LMALL_COUNT);
     else if (world > 1 && !c->multigraph) o.nland = std::min(n, 256);
     if (const char* e = getenv("SHD_ROUTE_LANDMARKS")) o.nland = c->multigraph ? 0 : std::max(0, std::min(atoi(e), n));
@@ -597,8 +597,8 @@ struct StageTimes {
 
 // the hub-row launch's grid for k rows: up to 256 in 1024-thread workgroups (one per CU) where
 // the context's are smaller, more in the context's own
-inline bool hub_big(const shd_route* c, int k) { return c->kd_hub_block > 0 && k <= 256; }
-inline int hub_grid(const shd_route* c, int k) { return std::min(k, hub_big(c, k) ? 256 : std::max(256, c->kd_slots)); }
+inline bool hub_big(const shd_route* c, int k) { return c->kd.hub_block > 0 && k <= 256; }
+inline int hub_grid(const shd_route* c, int k) { return std::min(k, hub_big(c, k) ? 256 : std::max(256, c->kd.slots)); }
 
 // the job records of a hub-row launch: no output row (row -1), row q kept in store slot q
 std::vector<KDJob> hub_jobs(const std::vector<int>& verts) {
@@ -645,7 +645,7 @@ int device_store_rows(shd_route* c, const std::vector<int>& verts, DevBuf& dd, D
     if (dj.alloc(sizeof(KDJob) * k) || dd.alloc(sizeof(uint16_t) * (size_t)rs * k) ||
         dp.alloc(sizeof(uint32_t) * (size_t)rs * k) || dn.alloc(sizeof(int) * (1 + (size_t)k)))
         return SHD_ROUTE_ENOMEM;
-    int rc = ensure_hub_ws(c, c->kd_stride * (size_t)grid);
+    int rc = ensure_hub_ws(c, c->kd.stride * (size_t)grid);
     if (rc) return rc;
     // (errors of earlier launches are reported by their own sync, not by this plan)
     if (hipDeviceSynchronize() != hipSuccess) return SHD_ROUTE_EDEVICE;
@@ -763,7 +763,7 @@ int lm_refresh(shd_route* c, const shd_route_plan* P, uint32_t what, hipStream_t
         // CU), then the others seeded from their three nearest of those (the main rows' seeding
         // rule, as the plan_lmall_jobs_kernel writes it), in the context's workgroups
         const int k0 = P->lm2, k1 = P->nhub - P->lm2;
-        if (!c->d_hub_ws || c->hub_ws_bytes < c->kd_stride * (size_t)std::max(hub_grid(c, k0), hub_grid(c, k1)))
+        if (!c->d_hub_ws || c->hub_ws_bytes < c->kd.stride * (size_t)std::max(hub_grid(c, k0), hub_grid(c, k1)))
             return SHD_ROUTE_EINVAL;
         if (hipMemsetAsync(P->d_hdone, 0, sizeof(int) * (1 + (size_t)P->nhub), st) != hipSuccess) return SHD_ROUTE_EDEVICE;
         DevDelta g = kd_args(c);
@@ -779,13 +779,13 @@ int lm_refresh(shd_route* c, const shd_route_plan* P, uint32_t what, hipStream_t
         if (hipMemsetAsync(P->d_hdone, 0, sizeof(int), st) != hipSuccess) return SHD_ROUTE_EDEVICE;  // (queue only)
         g.jobs = P->d_hjobs2;
         rc = kd_launch(c, g, P->d_hdone, nullptr, k1, nullptr, 0, 0, nullptr, nullptr, nullptr, st, true,
-                       c->d_hub_ws, std::min(k1, c->kd_slots), false);
+                       c->d_hub_ws, std::min(k1, c->kd.slots), false);
         if (rc) return rc;
     } else if ((what & SHD_ROUTE_REFRESH_ALL) || (what & SHD_ROUTE_REFRESH_MINE)) {
         const bool all = (what & SHD_ROUTE_REFRESH_ALL) != 0;
         const int q0 = all ? 0 : P->lm_first, k = all ? P->nhub : P->lm_count;
         // (the hub-row launch's scratch: the context's, grown at plan creation to this grid)
-        if (!c->d_hub_ws || c->hub_ws_bytes < c->kd_stride * (size_t)hub_grid(c, k)) return SHD_ROUTE_EINVAL;
+        if (!c->d_hub_ws || c->hub_ws_bytes < c->kd.stride * (size_t)hub_grid(c, k)) return SHD_ROUTE_EINVAL;
         if (hipMemsetAsync(P->d_hdone, 0, sizeof(int) * (1 + (size_t)P->nhub), st) != hipSuccess) return SHD_ROUTE_EDEVICE;
         DevDelta g = kd_args(c);
         g.jobs = P->d_hjobs + q0;  // (a job's store slot is its global landmark index)
@@ -886,8 +886,8 @@ int build_device_lm_plan(PlanBuild& B) {
         hipMalloc((void**)&P->d_jobs, sizeof(KDJob) * (size_t)nj) != hipSuccess ||
         hipMalloc((void**)&P->d_next, sizeof(int) * (1 + (size_t)nh)) != hipSuccess)
         return SHD_ROUTE_ENOMEM;
-    int rc = ensure_hub_ws(c, c->kd_stride * (size_t)std::max(std::max(P->hub_grid, hub_grid(c, std::max(1, P->lm_count))),
-                                                              P->lm2 ? std::max(hub_grid(c, P->lm2), std::min(nh - P->lm2, c->kd_slots)) : 0));
+    int rc = ensure_hub_ws(c, c->kd.stride * (size_t)std::max(std::max(P->hub_grid, hub_grid(c, std::max(1, P->lm_count))),
+                                                              P->lm2 ? std::max(hub_grid(c, P->lm2), std::min(nh - P->lm2, c->kd.slots)) : 0));
     if (rc) return rc;
     if (hipMemcpy(P->d_sq, sq.data(), sizeof(int) * nj, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(P->d_lv, lv.data(), sizeof(int) * nh, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1058,7 +1058,7 @@ bool device_seed_choices(const PlanBuild& B, const std::vector<int>& first, cons
         hipMemcpy(dav.p, av.data(), n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dsq.p, sq, sizeof(int) * nq, hipMemcpyHostToDevice) != hipSuccess)
         return false;
-    hipLaunchKernelGGL(plan_choice_kernel, dim3((nq + 3) / 4), dim3(256), 0, 0, c->d_row, c->d_kd_orec,
+    hipLaunchKernelGGL(plan_choice_kernel, dim3((nq + 3) / 4), dim3(256), 0, 0, c->d_row, c->kd.d_orec,
                        (const double*)dcl.p, (const int*)drk.p, (const uint8_t*)dav.p, (const int*)dsq.p, nq,
                        k, two_hop, hop_deg, B.o.alpha, cand, (PlanChoice*)dout.p);
     out.resize(nq);
@@ -1089,7 +1089,7 @@ void partition_forest(PlanBuild& B) {
     // of host CSR scans on every rank); SHD_ROUTE_GPUCHOICE=0 keeps the host scan
     std::vector<int> bu(ns, -1);
     std::vector<PlanChoice> ho;
-    if (B.o.gpu_choice && c->d_kd_orec != nullptr && device_seed_choices(B, first, src, ns, 1, 0, 0, 1, ho)) {
+    if (B.o.gpu_choice && c->kd.d_orec != nullptr && device_seed_choices(B, first, src, ns, 1, 0, 0, 1, ho)) {
         for (int p = 0; p < ns; p++) bu[p] = ho[p].m > 0 ? ho[p].u[0] : -1;
     } else {
         for (int p = 0; p < ns; p++) {
@@ -1452,7 +1452,7 @@ std::vector<KDJob> queue_jobs(PlanBuild& B) {
     B.T.mark("jobs");
     long long ticks = -1;
     const std::vector<int> order = list_schedule(nj, B.nsd.data(), B.lmseed.data(), std::move(deps),
-                                                 std::max(1, B.c->kd_slots), B.o.cost, B.o.sched, &ticks);
+                                                 std::max(1, B.c->kd.slots), B.o.cost, B.o.sched, &ticks);
     for (int qi = 0; qi < nj; qi++) {
         KDJob& J = jobs[qi];
         J = B.byjob[order[qi]];
@@ -1559,7 +1559,7 @@ int shd_route_plan_create(shd_route_t* c, const int32_t* src, int32_t ns, int32_
     P->c = c; P->world = world; P->rank = rank; P->ns_all = ns;
     P->delta = o.delta;
     PlanBuild B{c, src, ns, world, rank, o, P.get()};
-    B.want = o.seed && c->sel == 4 && c->kd_fused && !c->complete && !c->prefer_direct && ns >= 2 && !c->h_row.empty();
+    B.want = o.seed && c->sel == 4 && c->kd.fused && !c->complete && !c->prefer_direct && ns >= 2 && !c->h_row.empty();
     int rc;
     const int nmine = ns > rank ? (ns - rank + world - 1) / world : 0;
     if (B.want && o.lm_all && o.nland > 0 && nmine >= 2 && nmine <= PLAN_DEV_MAXJ && o.gpu_choice && o.lmall_rev &&
@@ -1607,7 +1607,7 @@ int shd_route_plan_get_info(const shd_route_plan_t* P, shd_route_plan_info_t* in
     info->world = P->world;
     info->rank = P->rank;
     info->store_bytes = P->store_bytes;
-    info->delta = P->seeded ? P->delta : P->c->kd_delta;
+    info->delta = P->seeded ? P->delta : P->c->kd.delta;
     info->pad_ = 0;
     return SHD_ROUTE_OK;
 }
