@@ -436,7 +436,9 @@ int shd_route_fw_table_async(shd_route_t* ctx, void* stream);
  * from the resident K4 table: lat from the table, the parent of each vertex by the
  * engine tie rule among its tight in-arcs, rel the source-first product down that
  * tree.  Same entries as shd_route_rows_async bit for bit (integer latencies).  Device
- * pointers; call shd_route_fw_table_async first (same stream or synchronised). */
+ * pointers; call shd_route_fw_table_async first (same stream or synchronised): without a
+ * table SHD_ROUTE_EINVAL, or SHD_ROUTE_EUNSUPPORTED on a graph K4 does not take (a multigraph
+ * among them); nothing is written either way. */
 int shd_route_fw_rows_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
                             int32_t nt, int64_t ld, double* d_lat, double* d_rel, double* d_row_min,
                             void* stream);

@@ -824,16 +824,26 @@ constexpr int kFwMaxN = 12000;  // fw_rows keeps rel f64 + order u16 per vertex 
 // ineligible graph, so every call answers EUNSUPPORTED), then the buffers into locals,
 // published in the context only when every step has succeeded; the in-list build is
 // enqueued on the caller's stream, ahead of the table launches that follow it there.
-int fw_prepare(shd_route* c, hipStream_t st) {
-    if (c->d_fwD) return SHD_ROUTE_OK;
+// K4 takes the graph: integer latencies below the u16 bound, no parallel edges, the rows' and the
+// in-list build's LDS state within the budget
+bool fw_eligible(const shd_route* c) {
     if (!c->integer_w || c->multigraph || c->n > kFwMaxN || c->k32.bound <= 0 || c->k32.bound >= 0xFFFF)
-        return SHD_ROUTE_EUNSUPPORTED;
+        return false;
     const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32.bound + 2));
-    if (lds > kLdsBudget) return SHD_ROUTE_EUNSUPPORTED;
+    if (lds > kLdsBudget) return false;
     const int np = (c->n + FW_T - 1) / FW_T * FW_T;
     int sp = 1;
     while (sp < np) sp <<= 1;
-    if ((size_t)4 * sp > kLdsBudget) return SHD_ROUTE_EUNSUPPORTED;
+    return (size_t)4 * sp <= kLdsBudget;
+}
+
+int fw_prepare(shd_route* c, hipStream_t st) {
+    if (c->d_fwD) return SHD_ROUTE_OK;
+    if (!fw_eligible(c)) return SHD_ROUTE_EUNSUPPORTED;
+    const size_t lds = a16(sizeof(double) * c->n) + a16(sizeof(uint16_t) * c->n) + a16(sizeof(int) * (c->k32.bound + 2));
+    const int np = (c->n + FW_T - 1) / FW_T * FW_T;
+    int sp = 1;
+    while (sp < np) sp <<= 1;
     int rc = ensure_dense(c);
     if (rc) return rc;
     if ((rc = hip_check(hipFuncSetAttribute((const void*)fw_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -985,7 +995,8 @@ int shd_route_fw_table_async(shd_route_t* c, void* stream) {
 int shd_route_fw_rows_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
                             int64_t ld, double* d_lat, double* d_rel, double* d_row_min, void* stream) {
     if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
-    if (!c->fw_ready) return SHD_ROUTE_EINVAL;  // shd_route_fw_table_async first
+    // (no table: a graph K4 never takes is unsupported; else shd_route_fw_table_async first)
+    if (!c->fw_ready) return fw_eligible(c) ? SHD_ROUTE_EINVAL : SHD_ROUTE_EUNSUPPORTED;
     if (ns == 0) return SHD_ROUTE_OK;
     if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
     hipStream_t st = (hipStream_t)stream;

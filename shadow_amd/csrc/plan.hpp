@@ -548,6 +548,10 @@ PlanOptions plan_options(const shd_route* c, int ns, int world) {
     if (const char* e = getenv("SHD_ROUTE_LMALL")) lmall_rps = atof(e);
     int lmall_small = 1;
     if (const char* e = getenv("SHD_ROUTE_LMALL_SMALL")) lmall_small = atoi(e);
+    // (the multigraph terms below, like the duplicate-head notes at plan_choice_kernel and at the
+    // host's candidate order, never decide anything: a seeded plan needs KD (shd_route_plan_create:
+    // sel == 4), and select_inrows gives a multigraph no integer kernel, so its plans are plain
+    // rows before any of these options is read -- tests/test_multi_gpu.py test_plans_fall_back)
     o.lm_all = !c->multigraph && c->kd.slots > 0 &&
                ((lmall_small && c->kd.block < 1024 && n >= 2048) ||
                 (double)ns / world <= lmall_rps * (double)c->kd.slots);

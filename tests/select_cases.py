@@ -8,6 +8,8 @@ host-only selection against it without a GPU, and test_select_gpu.py the created
   frac1024 / frac5000 / frac20000   two-decimal latencies: KF with 256 threads, KF with 1024,
                                     KFH (the per-vertex state in HBM)
   lat75k                            integer latencies up to 75000 (no u16 kernel takes them)
+  the multigraphs of multi_graphs.SUITE (all but multi_k24) with a clean environment: no integer
+                                    kernel takes parallel edges or a second self-loop
   the overrides below, each on the graphs whose decision it can move
 """
 from __future__ import annotations
@@ -16,7 +18,7 @@ import dataclasses
 
 from shadow_amd.graph import Graph, fractional
 
-from . import range_graphs, shape_graphs
+from . import multi_graphs, range_graphs, shape_graphs
 
 # what the fixture records of Engine.info
 FIELDS = ("kernel", "block", "reserved", "dist_bound", "lat16", "lds_resident", "device_bytes",
@@ -35,6 +37,9 @@ EXTRA = {
     "lat75k": _lat75k,
 }
 
+MULTI = ("multi389", "multi389_dir", "multi389_frac", "multi389_vloss", "multi389_manyrel", "loops_only",
+         "multi8000", "count_complete")
+
 _cache: dict = {}
 
 
@@ -43,6 +48,8 @@ def graph(name: str) -> Graph:
         return shape_graphs.get(name)
     if name in range_graphs.SUITE:
         return range_graphs.get(name)
+    if name in MULTI:
+        return multi_graphs.get(name)
     if name not in _cache:
         _cache[name] = EXTRA[name]()
     return _cache[name]
@@ -82,6 +89,13 @@ def _cases():
     add("frac1024", KERNEL="kf")
     add("frac1024", KERNEL="f64")
     add("frac1024", KERNEL="kd")
+    for g in MULTI:
+        c[g] = (g, {})
+    for g in ("multi389", "multi389_frac"):
+        add(g, KERNEL="kd")
+        add(g, KERNEL="kf")
+        add(g, KFH=1)
+        add(g, KFH=1, KFPK=0)
     return c
 
 

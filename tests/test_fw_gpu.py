@@ -149,7 +149,7 @@ def test_fw_ineligible_stays_unsupported():
     lat = torch.empty((1, 1), dtype=torch.float64, device=dev)
     with pytest.raises(route.RouteError) as e:
         eng.fw_rows_async(S, S, lat, lat.clone(), None)
-    assert e.value.code == route.EINVAL
+    assert e.value.code == route.EUNSUPPORTED
 
 
 def test_fw_on_side_stream(oracle_mod):

@@ -127,3 +127,21 @@ def test_prefer_direct_attribute(topo, tmp_path):
     to_graphml(g, str(p))
     h = topo.load_graphml(str(p))
     assert h.prefer_direct and np.array_equal(h.latency, g.latency)
+
+
+@pytest.mark.parametrize("name", ["multi389", "multi389_dir"])
+def test_parallel_edges_keep_document_order(topo, tmp_path, name):
+    """Parallel <edge> elements and repeated self-loops stay in document order, which is the
+    edge-id order the tie rule and the direct tables go by (tests/multi_graphs.py)."""
+    from tests import multi_graphs as mg
+    g = mg.get(name)
+    p = tmp_path / f"{name}.graphml.xml"
+    to_graphml(g, str(p))
+    h = topo.load_graphml(str(p))
+    assert h.n == g.n and h.m == g.m and h.directed == g.directed
+    assert np.array_equal(h.src, g.src) and np.array_equal(h.dst, g.dst)
+    assert np.array_equal(h.latency, g.latency) and np.array_equal(h.packetloss, g.packetloss)
+    assert h.vertex_packetloss is None or np.isnan(h.vertex_packetloss).all()
+    key = np.stack([np.minimum(g.src, g.dst), np.maximum(g.src, g.dst)] if not g.directed else [g.src, g.dst], axis=1)
+    _, cnt = np.unique(key, axis=0, return_counts=True)
+    assert (cnt > 1).sum() > 500          # the file does hold parallel edges
