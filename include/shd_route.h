@@ -14,6 +14,41 @@
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
  * rows launch inside and fall under the same rule.
  *
+ * Several contexts may be alive in one process, on one device or on several, each used as
+ * above; creating, using and destroying one never changes what another computes.  (A context
+ * sets the dynamic-LDS limit of its kernel functions to its own size when it is created, or at
+ * its first hops / K4 call; the limit belongs to the function, so a later, smaller context
+ * lowers it.  The ROCm runtime this was tried on (gfx950) does not hold a launch to that
+ * attribute -- a launch of up to the 160 KiB the device has goes through whatever the last
+ * value was -- and tests/test_contexts_gpu.py keeps pairs of contexts that ask for 3 to over
+ * 100 times different amounts, up to the full 160 KiB, alive together for every such kernel.)
+ * shd_route_destroy frees device memory, which waits for the device: it may block while other
+ * contexts' work is queued, and that work is not disturbed.
+ *
+ * Stream order of the *_async calls.  Everything such a call does on the device -- its
+ * kernels, the zeroing of its counters, flags and outputs, the parking of the error word --
+ * is enqueued on the caller's stream, and the call reads its device inputs only there:
+ * inputs written by earlier work of the same stream are seen, and calls of one context may be
+ * chained on one stream without a host synchronisation (any stream, the non-blocking ones
+ * included; tests/test_stream_gpu.py).  In its steady state no *_async call waits for the
+ * device.  The calls that may block the host, and when:
+ *   first use      shd_route_rows_async with SHD_ROUTE_DISPATCH on a complete graph,
+ *                  shd_route_fw_table_async (the dense tables, built on the host and copied);
+ *                  the hops and loads calls (their in-CSR with edge ids); all once per context
+ *   scratch growth a call that needs more scratch than the context holds frees the old block
+ *                  (which waits for the device) and allocates: shd_route_rows_async under KB
+ *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
+ *                  the hops and loads calls when their source chunk grows, shd_route_loads_async
+ *                  in its HBM form when the slices grow (that one synchronises the stream)
+ * A first call with the largest sizes takes both out of the way.
+ * Capture: after such a first call, shd_route_rows_async (every kernel),
+ * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
+ * shd_route_plan_refresh_async and shd_route_min_reduce_async enqueue only kernels and
+ * memsets and can be captured into a graph (hipStreamBeginCapture on the stream they are
+ * given); inputs are read when the graph runs, so a replay sees what its buffers hold then.
+ * A call that would grow scratch or build tables must not be made while capturing; the
+ * blocking calls and shd_route_sync are not capturable.
+ *
  * Reference interface each entry point replaces (file:line in the reference):
  *   shd_route_create   <- _topology_loadGraph/_topology_checkGraph/_topology_extractEdgeWeights
  *                         (topology.c:371-399, 1187-1246): graph in, validated, resident

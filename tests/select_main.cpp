@@ -50,6 +50,7 @@ int main(int argc, char** argv) {
     num("n", h.n); num("nnz", h.nnz); num("directed", h.directed); num("integer_w", h.integer_w);
     num("multigraph", h.multigraph); num("self16", h.self16); real("min_w", h.min_w);
     num("f64.lds", kSmallBytes + StateLayout::make(n).total <= kLdsBudget); num("f64.block", kBlock);
+    num("f64.bytes", (long long)(kSmallBytes + StateLayout::make(n).total));
     num("sel", s.sel); num("upload_bytes", (long long)s.upload_bytes);
     num("inrows.ok", s.inrows.ok); num("inrows.bound", s.inrows.bound);
     num("k32.staged", s.k32.staged); num("k32.ok", s.k32.ok); num("k32.block", s.k32.block);
