@@ -12,12 +12,13 @@
  * per-workgroup scratch, so two of them must not be in flight together (enqueue them
  * on one stream, or synchronise in between).  The path hops calls (shd_route_hops*,
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
- * rows launch inside and fall under the same rule.
+ * rows launch inside and fall under the same rule, and so do the tie envelope calls
+ * (shd_route_ties*).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
  * sets the dynamic-LDS limit of its kernel functions to its own size when it is created, or at
- * its first hops / K4 call; the limit belongs to the function, so a later, smaller context
+ * its first hops / ties / K4 call; the limit belongs to the function, so a later, smaller context
  * lowers it.  The ROCm runtime this was tried on (gfx950) does not hold a launch to that
  * attribute -- a launch of up to the 160 KiB the device has goes through whatever the last
  * value was -- and tests/test_contexts_gpu.py keeps pairs of contexts that ask for 3 to over
@@ -34,12 +35,14 @@
  * device.  The calls that may block the host, and when:
  *   first use      shd_route_rows_async with SHD_ROUTE_DISPATCH on a complete graph,
  *                  shd_route_fw_table_async (the dense tables, built on the host and copied);
- *                  the hops and loads calls (their in-CSR with edge ids); all once per context
+ *                  the hops, loads and ties calls (their in-CSR with edge ids; the ties calls
+ *                  also their per-arc reliabilities and out-CSR); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
- *                  the hops and loads calls when their source chunk grows, shd_route_loads_async
- *                  in its HBM form when the slices grow (that one synchronises the stream)
+ *                  the hops, loads and ties calls when their source chunk grows,
+ *                  shd_route_loads_async and shd_route_ties_async in their HBM forms when the
+ *                  slices grow (those synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -67,6 +70,8 @@
  *   shd_route_fw       <- (no reference equivalent; dense all-pairs alternative)
  *   shd_route_loads, shd_route_pair_loads <- (no reference equivalent; per-link and
  *                         per-router traffic of the chosen paths)
+ *   shd_route_ties     <- (no reference equivalent; how many shortest paths tie and how far
+ *                         any tie rule, igraph's heap order included, can move reliability)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -264,6 +269,50 @@ int shd_route_loads(shd_route_t* ctx, const int32_t* src, int32_t ns, const int3
 int shd_route_pair_loads(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
                          const uint64_t* pair_wt, int64_t npairs, uint32_t flags, uint64_t* edge_load_out,
                          uint64_t* transit_out, uint64_t* unrouted_out);
+
+/* ---- tie envelope: path counts and reliability bounds over tied shortest paths ------------
+ * No reference equivalent: the reference keeps the one path igraph's heap pop order leaves it
+ * with (topology.c:1756), the engine the one its tie rule above picks.  These calls say what
+ * every tie rule could give.  Entries are those of shd_route_hops*, same flags.
+ *   A shortest path s -> t (t != s) is a sequence of arcs u -> v over an edge e with
+ * d[u] + w_e == d[v] in f64, d the all-vertex latency row of shd_route_rows_async for s (no
+ * dispatch, any selected kernel) with d[s] taken as 0.0.  Self-loops are not arcs; parallel
+ * tight edges are distinct paths.
+ *   t != s : count = the number of such paths, a u64 that saturates at 2^64 - 1 (a saturated
+ *            summand keeps the sum saturated); rel_lo / rel_hi = the min / max over those paths
+ *            of (1.0*f_s)*r_1*r_2*... folded from the source, then multiplied by f_t last when
+ *            the target has a vertex factor; absent factors are skipped.  Computed as
+ *            lo[s] = hi[s] = 1.0*f_s, lo[v] = min over the tight in-arcs of lo[u]*r_e (hi: max),
+ *            count[v] = the saturating sum of count[u].  Reliabilities are in [0, 1], so
+ *            fl(a*r) is monotone in a and the programme's bounds are the exact min and max of
+ *            the paths' left folds, bit for bit: the rel of shd_route_rows lies in
+ *            [rel_lo, rel_hi] (to the bit where f_t is absent or 1.0, within a few ulp
+ *            otherwise) and equals both where count == 1.
+ *   t == s : count 1, rel_lo == rel_hi == the batch self entry's reliability (the lowest-id
+ *            self-loop, (1.0*f_s)*r_ss); without a self-loop count 0, NaN and SHD_ROUTE_ENOEDGE.
+ *   unreachable t : count 0, NaN and SHD_ROUTE_EUNREACH.
+ * With SHD_ROUTE_DISPATCH a complete graph, or prefer-direct with an adjacent pair, gives
+ * count 1 and both bounds = ((1.0*f_s)*f_t)*r over the lowest edge id joining the pair; on a
+ * complete graph no rows launch and no sweep run (a pair without an edge: SHD_ROUTE_ENOEDGE).
+ * Failed entries never stop the rest from being written; the code is returned at the end
+ * (shd_route_ties) or by the next shd_route_sync (shd_route_ties_async).
+ * The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the hops calls' scratch: per source of a chunk an f64 distance row and a u32 row (the
+ * tight in-degree of every vertex, in the parent row's place), chunks sized to
+ * SHD_ROUTE_HOPS_SCRATCH (1 GiB).  One workgroup per source sweeps the DAG of tight arcs level
+ * by level; its state (32 bytes per vertex while n <= 65535, 36 above) lives in LDS or, on
+ * larger graphs and with SHD_ROUTE_TIES_LDS=0, in HBM slices of 16 to 512 workgroup slots
+ * within a quarter of that budget.  The rounds equal the deepest tied path in hops.
+ * Diagnostic rate: every call runs the sources' SSSP. */
+
+/* d_count / d_rel_lo / d_rel_hi[i*ld + j] of src[i] -> tgt[j]; any output may be NULL.  Device
+ * pointers, as shd_route_hops_async. */
+int shd_route_ties_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                         int32_t nt, int64_t ld, uint32_t flags, uint64_t* d_count, double* d_rel_lo,
+                         double* d_rel_hi, void* stream);
+/* Same with host pointers (row stride nt); blocks. */
+int shd_route_ties(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                   uint32_t flags, uint64_t* count_out, double* rel_lo_out, double* rel_hi_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

@@ -180,6 +180,39 @@ int shd_topology_dump_link_loads(shd_topology_t* top, FILE* out);
 int64_t shd_topology_link_line(char** buf, size_t* cap, char* const* names, int32_t edge, int32_t a, int32_t b,
                                double latency, double loss, uint64_t packets, int directed);
 
+/* ---- tie envelope: how much of the cached reliabilities hangs on a tie-break ---------------
+ * No reference equivalent.  Where several shortest paths tie on latency the reference keeps
+ * the one igraph's heap order returns and the engine the one of its own rule; shd_route_ties
+ * (shd_route.h) gives, per pair, the number of shortest paths and the smallest and largest
+ * reliability any of them has.  These calls run it over the cache's stored off-diagonal pairs:
+ * the sorted attached vertices A, pair i < j as source A[i] -> target A[j] (the orientation
+ * the first writer stored), with the dispatch the cache used.  Like the link loads they run on
+ * engine 0 under the topology lock, in chunks of sources, compute on demand, cache nothing and
+ * change no accessor. */
+typedef struct shd_tie_stats {
+    uint64_t pairs;      /* stored off-diagonal pairs that have a path */
+    uint64_t tied;       /* of them: more than one shortest path */
+    uint64_t sensitive;  /* of them: rel_lo != rel_hi, the reliability depends on the tie rule */
+    uint64_t saturated;  /* of them: the path count reached 2^64 - 1 */
+    double max_spread;   /* the largest (rel_hi - rel_lo) / rel_hi; 0 without a sensitive pair */
+    int32_t worst_src, worst_dst; /* the pair attaining it, the lowest (src, dst) among equals; -1, -1 */
+    uint64_t worst_count;         /* its path count, */
+    double worst_lo, worst_hi;    /* and bounds (0 without a sensitive pair) */
+} shd_tie_stats_t;
+int shd_topology_tie_stats(shd_topology_t* top, shd_tie_stats_t* out);
+/* One line per sensitive pair, in (src, dst) order, then the summary line:
+ *   tie A<-->B (i<-->j) has N shortest paths, reliability LO to HI, spread S
+ *   ties: P pairs, T tied, S sensitive, U saturated, max spread X at (i<-->j) with N paths
+ * ("-->" on directed graphs; names as in the route line; %.17g numbers; a saturated count ends
+ * in '+'). */
+int shd_topology_dump_ties(shd_topology_t* top, FILE* out);
+/* The formatters alone, pure host functions (tie_fmt.c); names and the growable *buf / *cap
+ * as shd_topology_route_line.  Return the length without the NUL, -1 on a bad argument or
+ * allocation failure. */
+int64_t shd_topology_tie_line(char** buf, size_t* cap, char* const* names, int32_t a, int32_t b, uint64_t count,
+                              double rel_lo, double rel_hi, int directed);
+int64_t shd_topology_tie_summary_line(char** buf, size_t* cap, const shd_tie_stats_t* st, int directed);
+
 #ifdef __cplusplus
 }
 #endif

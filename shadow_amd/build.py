@@ -22,7 +22,7 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-ffp-contract=off", "-f
 
 FRONT_SOURCES = [os.path.join(HERE, "csrc", "graphml.c"), os.path.join(HERE, "csrc", "topology_front.c"),
                  os.path.join(HERE, "csrc", "attach.c"), os.path.join(HERE, "csrc", "route_fmt.c"),
-                 os.path.join(HERE, "csrc", "link_fmt.c")]
+                 os.path.join(HERE, "csrc", "link_fmt.c"), os.path.join(HERE, "csrc", "tie_fmt.c")]
 FRONT_OUT = os.path.join(HERE, "libshd_topology.so")
 CC = os.environ.get("CC", "gcc")
 

@@ -23,6 +23,7 @@
 #include "fw.hpp"
 #include "path_hops.hpp"
 #include "link_loads.hpp"
+#include "path_ties.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 
@@ -156,6 +157,11 @@ struct shd_route {
     // link loads (link_loads.hpp): the workgroup slices of the tree sums' HBM form
     int ld_ready = 0;
     char* d_ld_ws = nullptr; size_t ld_ws_cap = 0;
+    // tie envelope (path_ties.hpp): per-in-arc reliabilities aligned with the hops in-CSR and the
+    // out-CSR of the release pass (built at the first ties call), the HBM form's workgroup slices
+    int ti_ready = 0;
+    double* d_ti_r = nullptr; int* d_ti_row = nullptr; int* d_ti_head = nullptr; double* d_ti_w = nullptr;
+    char* d_ti_ws = nullptr; size_t ti_ws_cap = 0;
     uint64_t device_bytes = 0;
     // host copies needed for lazy dense build
     std::vector<int32_t> e_src, e_dst;
@@ -593,6 +599,7 @@ void shd_route_destroy(shd_route_t* c) {
     if (c->d_hp_ws) (void)hipFree(c->d_hp_ws);
     if (c->d_hp_buf) (void)hipFree(c->d_hp_buf);
     if (c->d_ld_ws) (void)hipFree(c->d_ld_ws);
+    if (c->d_ti_ws) (void)hipFree(c->d_ti_ws);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
 }
@@ -1997,6 +2004,204 @@ int shd_route_pair_loads(shd_route_t* c, const int32_t* pair_src, const int32_t*
     int soft = shd_route_sync(c, nullptr);
     if (soft && soft != SHD_ROUTE_ENOEDGE && soft != SHD_ROUTE_EUNREACH) return soft;
     if ((rc = out.finish(flags, edge_load_out, transit_out, unrouted_out))) return rc;
+    return soft;
+}
+
+}  // extern "C"
+
+// =============================================================================
+// Tie envelope (path_ties.hpp): path counts and reliability bounds over tied paths
+// =============================================================================
+namespace {
+
+// the reliabilities of the hops in-CSR's arcs (the same order: head, tail, edge id) and the
+// out-CSR (tail, head, edge id) without self-loops, parallel arcs kept
+int ensure_ties(shd_route* c) {
+    if (c->ti_ready) return SHD_ROUTE_OK;
+    int rc = ensure_hops(c);
+    if (rc) return rc;
+    const int n = c->n;
+    std::vector<int> head, tail, eid;
+    for (int e = 0; e < c->m; e++) {
+        const int a = c->e_src[e], b = c->e_dst[e];
+        if (a == b) continue;
+        head.push_back(b); tail.push_back(a); eid.push_back(e);
+        if (!c->directed) { head.push_back(a); tail.push_back(b); eid.push_back(e); }
+    }
+    const size_t k = head.size();
+    std::vector<size_t> idx(k);
+    std::iota(idx.begin(), idx.end(), 0);
+    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
+        if (head[x] != head[y]) return head[x] < head[y];
+        if (tail[x] != tail[y]) return tail[x] < tail[y];
+        return eid[x] < eid[y];
+    });
+    std::vector<double> r(k);
+    for (size_t q = 0; q < k; q++) r[q] = c->e_rel[eid[idx[q]]];
+    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
+        if (tail[x] != tail[y]) return tail[x] < tail[y];
+        if (head[x] != head[y]) return head[x] < head[y];
+        return eid[x] < eid[y];
+    });
+    std::vector<int> row(n + 1, 0), hd(k);
+    std::vector<double> w(k);
+    for (size_t q = 0; q < k; q++) {
+        const size_t a = idx[q];
+        row[tail[a] + 1]++;
+        hd[q] = head[a];
+        w[q] = c->e_lat[eid[a]];
+    }
+    for (int v = 0; v < n; v++) row[v + 1] += row[v];
+    rc = upload(c, &c->d_ti_r, r);
+    if (!rc) rc = upload(c, &c->d_ti_row, row);
+    if (!rc) rc = upload(c, &c->d_ti_head, hd);
+    if (!rc) rc = upload(c, &c->d_ti_w, w);
+    if (!rc && ties_fits_lds(n))
+        rc = hip_check(hipFuncSetAttribute((const void*)ties_dag_kernel<uint16_t, true, 1024>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(kTiSmall + TiesLayout<uint16_t>::make(n).total)));
+    if (rc) return rc;
+    c->ti_ready = 1;
+    return SHD_ROUTE_OK;
+}
+
+DevTies dev_ties(const shd_route* c) {
+    DevTies q;
+    q.r_in = c->d_ti_r; q.row_out = c->d_ti_row; q.head_out = c->d_ti_head; q.w_out = c->d_ti_w;
+    q.vf = c->d_vf; q.self_r = c->d_self_r;
+    return q;
+}
+
+// dist (k x n f64) = the all-vertex latency rows of the sources, rem (k x n u32) the tight
+// in-degree of every vertex under each
+int ti_rows(shd_route* c, const int32_t* d_src, int k, double* dist, uint32_t* rem, hipStream_t st) {
+    const int n = c->n;
+    hipLaunchKernelGGL(hops_err_park_kernel, dim3(1), dim3(1), 0, st, c->d_err, c->d_hp_saved);
+    int rc = shd_route_rows_async(c, d_src, k, c->d_hp_ident, n, n, 0u, dist, nullptr, nullptr, st);
+    hipLaunchKernelGGL(hops_err_unpark_kernel, dim3(1), dim3(1), 0, st, c->d_err, (const int*)c->d_hp_saved);
+    if (rc) return rc;
+    const dim3 grid((unsigned)std::min((n + 255) / 256, 4096), (unsigned)std::min(k, 65535));
+    hipLaunchKernelGGL(ties_indeg_kernel<256>, grid, dim3(256), 0, st, dev_hops(c), (const double*)dist, (long long)n,
+                       d_src, k, rem, (long long)n);
+    return hip_check(hipGetLastError());
+}
+
+// the sweep of k sources and their entries (ties_dag_kernel), state in LDS or in HBM slices
+int ti_dag(shd_route* c, const double* dist, const uint32_t* rem, const int32_t* d_src, int k, const int32_t* d_tgt,
+           int nt, long long ld, int mode, uint64_t* d_count, double* d_lo, double* d_hi, hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    const DevTies q = dev_ties(c);
+    auto* cnt = (unsigned long long*)d_count;
+    if (mode == 2) {  // no rows, no DAG, no state
+        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, false, 1024>), dim3(std::min(k, 1024)), dim3(1024), kTiSmall, st,
+                           g, q, dist, rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, (char*)nullptr, (size_t)0,
+                           c->d_err);
+        return hip_check(hipGetLastError());
+    }
+    const bool small = n <= 65535;
+    const size_t lds_bytes = kTiSmall + TiesLayout<uint16_t>::make(n).total;
+    const char* e = getenv("SHD_ROUTE_TIES_LDS");  // "0": the HBM form on graphs the LDS form takes
+    if (ties_fits_lds(n) && !(e && *e && atoi(e) == 0)) {
+        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, true, 1024>), dim3(std::min(k, 1024)), dim3(1024), lds_bytes, st,
+                           g, q, dist, rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, (char*)nullptr, (size_t)0,
+                           c->d_err);
+        return hip_check(hipGetLastError());
+    }
+    // HBM slices: a quarter of the hops scratch budget, 16 to 512 workgroup slots (as the loads)
+    const size_t stride = a16(small ? TiesLayout<uint16_t>::make(n).total : TiesLayout<uint32_t>::make(n).total);
+    const int slots = (int)std::max<size_t>(16, std::min<size_t>(512, hp_budget() / 4 / stride));
+    const int grid = std::min(k, slots);
+    if (stride * (size_t)grid > c->ti_ws_cap) {
+        // a launch of this context that still uses the old slices is on the same stream or
+        // synchronised (one rows launch at a time): wait before the slices go
+        if (c->d_ti_ws) {
+            if (hipStreamSynchronize(st) != hipSuccess) return SHD_ROUTE_EDEVICE;
+            (void)hipFree(c->d_ti_ws);
+        }
+        c->d_ti_ws = nullptr;
+        c->ti_ws_cap = 0;
+        if (hipMalloc((void**)&c->d_ti_ws, stride * (size_t)slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
+        c->ti_ws_cap = stride * (size_t)slots;
+    }
+    if (small)
+        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, false, 1024>), dim3(grid), dim3(1024), kTiSmall, st, g, q, dist,
+                           rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, c->d_ti_ws, stride, c->d_err);
+    else
+        hipLaunchKernelGGL((ties_dag_kernel<uint32_t, false, 1024>), dim3(grid), dim3(1024), kTiSmall, st, g, q, dist,
+                           rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, c->d_ti_ws, stride, c->d_err);
+    return hip_check(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_ties_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                         int64_t ld, uint32_t flags, uint64_t* d_count, double* d_rel_lo, double* d_rel_hi,
+                         void* stream) {
+    if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
+    if (ns == 0) return SHD_ROUTE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    int rc = ensure_ties(c);
+    if (rc) return rc;
+    const int mode = hp_mode(c, flags);
+    if (mode == 2)
+        return ti_dag(c, nullptr, nullptr, d_src, ns, d_tgt, nt, (long long)ld, 2, d_count, d_rel_lo, d_rel_hi, st);
+    const size_t per = (size_t)c->n * (sizeof(double) + sizeof(uint32_t));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)ns, hp_budget() / per));
+    if ((rc = hp_scratch(c, per * (size_t)chunk))) return rc;
+    double* dist = (double*)c->d_hp_buf;
+    uint32_t* rem = (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)c->n * (size_t)chunk);
+    for (int i0 = 0; i0 < ns; i0 += chunk) {
+        const int k = std::min(chunk, ns - i0);
+        if ((rc = ti_rows(c, d_src + i0, k, dist, rem, st))) return rc;
+        if ((rc = ti_dag(c, dist, rem, d_src + i0, k, d_tgt, nt, (long long)ld, mode,
+                         d_count ? d_count + (long long)i0 * ld : nullptr,
+                         d_rel_lo ? d_rel_lo + (long long)i0 * ld : nullptr,
+                         d_rel_hi ? d_rel_hi + (long long)i0 * ld : nullptr, st)))
+            return rc;
+    }
+    return SHD_ROUTE_OK;
+}
+
+int shd_route_ties(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
+                   uint64_t* count_out, double* rel_lo_out, double* rel_hi_out) {
+    if (!c || ns < 0 || nt < 0 || (ns && !src) || (nt && !tgt)) return SHD_ROUTE_EINVAL;
+    if (ns == 0) return SHD_ROUTE_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // rows of the three outputs per device chunk: up to 1 GiB
+    const size_t row_elems = (size_t)std::max(nt, 1);
+    const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / (24 * row_elems)));
+    DevBuf dsrc, dtgt, dc, dl, dh;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * ns)) || (rc = dtgt.alloc(sizeof(int32_t) * std::max(nt, 1))) ||
+        (count_out && (rc = dc.alloc(sizeof(uint64_t) * row_elems * chunk))) ||
+        (rel_lo_out && (rc = dl.alloc(sizeof(double) * row_elems * chunk))) ||
+        (rel_hi_out && (rc = dh.alloc(sizeof(double) * row_elems * chunk))))
+        return rc;
+    if (hipMemcpy(dsrc.p, src, sizeof(int32_t) * ns, hipMemcpyHostToDevice) != hipSuccess ||
+        (nt && hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess))
+        return SHD_ROUTE_EDEVICE;
+    int soft = SHD_ROUTE_OK;
+    for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
+        const int32_t k = std::min(chunk, ns - i0);
+        rc = shd_route_ties_async(c, (const int32_t*)dsrc.p + i0, k, (const int32_t*)dtgt.p, nt, nt, flags,
+                                  count_out ? (uint64_t*)dc.p : nullptr, rel_lo_out ? (double*)dl.p : nullptr,
+                                  rel_hi_out ? (double*)dh.p : nullptr, nullptr);
+        if (rc) return rc;
+        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
+        if (rc && !soft) soft = rc;
+        const size_t cnt = (size_t)nt * k;
+        if (nt && ((count_out && hipMemcpy(count_out + (size_t)i0 * nt, dc.p, sizeof(uint64_t) * cnt,
+                                           hipMemcpyDeviceToHost) != hipSuccess) ||
+                   (rel_lo_out && hipMemcpy(rel_lo_out + (size_t)i0 * nt, dl.p, sizeof(double) * cnt,
+                                            hipMemcpyDeviceToHost) != hipSuccess) ||
+                   (rel_hi_out && hipMemcpy(rel_hi_out + (size_t)i0 * nt, dh.p, sizeof(double) * cnt,
+                                            hipMemcpyDeviceToHost) != hipSuccess)))
+            return SHD_ROUTE_EDEVICE;
+    }
     return soft;
 }
 

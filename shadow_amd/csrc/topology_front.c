@@ -817,6 +817,77 @@ int shd_topology_dump_link_loads(shd_topology_t* t, FILE* out) {
     return rc;
 }
 
+/* ---- tie envelope over the stored off-diagonal pairs (shd_route_ties on engine 0, in chunks
+ * of sources, nothing cached); `out`: also one line per sensitive pair ---- */
+
+#define TIE_CHUNK_BYTES ((size_t)64 << 20)  /* count, rel_lo, rel_hi rows per shd_route_ties call */
+
+static int ties_pass(shd_topology_t* t, shd_tie_stats_t* st, FILE* out) {
+    memset(st, 0, sizeof *st);
+    st->worst_src = st->worst_dst = -1;
+    pcache* c = cache_of(t);
+    if (!c) return SHD_ROUTE_EDEVICE;
+    const int32_t na = c->na;
+    if (na < 2) return SHD_ROUTE_OK;
+    size_t rows = TIE_CHUNK_BYTES / (24 * (size_t)na);
+    if (rows < 1) rows = 1;
+    if (rows > (size_t)na) rows = (size_t)na;
+    uint64_t* cnt = malloc(sizeof(uint64_t) * rows * (size_t)na);
+    double* lo = malloc(sizeof(double) * rows * (size_t)na);
+    double* hi = malloc(sizeof(double) * rows * (size_t)na);
+    char* line = NULL;
+    size_t lcap = 0;
+    int rc = (cnt && lo && hi) ? SHD_ROUTE_OK : SHD_ROUTE_ENOMEM;
+    for (int32_t i0 = 0; i0 < na - 1 && !rc; i0 += (int32_t)rows) {
+        const int32_t k = (int32_t)rows < na - 1 - i0 ? (int32_t)rows : na - 1 - i0;
+        pthread_mutex_lock(&t->lock);
+        rc = shd_route_ties(t->eng[0], c->A + i0, k, c->A, na, SHD_ROUTE_DISPATCH, cnt, lo, hi);
+        pthread_mutex_unlock(&t->lock);
+        /* a self pair without a self-loop, an unreachable pair: not among the pairs counted */
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;
+        for (int32_t i = i0; i < i0 + k && !rc; i++)
+            for (int32_t j = i + 1; j < na; j++) {
+                const size_t q = (size_t)(i - i0) * (size_t)na + (size_t)j;
+                if (!cnt[q]) continue;
+                st->pairs++;
+                if (cnt[q] > 1) st->tied++;
+                if (cnt[q] == UINT64_MAX) st->saturated++;
+                if (lo[q] == hi[q]) continue;
+                st->sensitive++;
+                const double spread = (hi[q] - lo[q]) / hi[q];
+                if (spread > st->max_spread) {
+                    st->max_spread = spread;
+                    st->worst_src = c->A[i]; st->worst_dst = c->A[j];
+                    st->worst_count = cnt[q]; st->worst_lo = lo[q]; st->worst_hi = hi[q];
+                }
+                if (!out) continue;
+                const int64_t len = shd_topology_tie_line(&line, &lcap, t->gml.vertex_ids, c->A[i], c->A[j], cnt[q], lo[q],
+                                                          hi[q], t->directed);
+                if (len < 0) { rc = SHD_ROUTE_ENOMEM; break; }
+                fwrite(line, 1, (size_t)len, out);
+                fputc('\n', out);
+            }
+    }
+    if (!rc && out) {
+        const int64_t len = shd_topology_tie_summary_line(&line, &lcap, st, t->directed);
+        if (len < 0) rc = SHD_ROUTE_ENOMEM;
+        else { fwrite(line, 1, (size_t)len, out); fputc('\n', out); }
+    }
+    free(cnt); free(lo); free(hi); free(line);
+    return rc;
+}
+
+int shd_topology_tie_stats(shd_topology_t* t, shd_tie_stats_t* out) {
+    if (!t || !out) return SHD_ROUTE_EINVAL;
+    return ties_pass(t, out, NULL);
+}
+
+int shd_topology_dump_ties(shd_topology_t* t, FILE* out) {
+    if (!t || !out) return SHD_ROUTE_EINVAL;
+    shd_tie_stats_t st;
+    return ties_pass(t, &st, out);
+}
+
 int shd_topology_dump_paths(shd_topology_t* t, FILE* out) {
     if (!t || !out) return SHD_ROUTE_EINVAL;
     pcache* c = cache_of(t);

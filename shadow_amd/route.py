@@ -85,6 +85,7 @@ EXPORTS = (
     "shd_route_host_unpinned", "shd_route_plan_refresh_async", "shd_route_plan_landmarks",
     "shd_route_plan_bind_store", "shd_route_hops_async", "shd_route_hops", "shd_route_paths",
     "shd_route_plan_jobs", "shd_route_loads_async", "shd_route_loads", "shd_route_pair_loads",
+    "shd_route_ties_async", "shd_route_ties",
 )
 
 _lib = None
@@ -169,6 +170,10 @@ def load_library():
     L.shd_route_loads.argtypes = [P, P, I32, P, I32, U32, P, P, P, P]
     L.shd_route_pair_loads.restype = C.c_int
     L.shd_route_pair_loads.argtypes = [P, P, P, P, I64, U32, P, P, P]
+    L.shd_route_ties_async.restype = C.c_int
+    L.shd_route_ties_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P]
+    L.shd_route_ties.restype = C.c_int
+    L.shd_route_ties.argtypes = [P, P, I32, P, I32, U32, P, P, P]
     _lib = L
     return L
 
@@ -281,6 +286,24 @@ class RouteEngine:
         _check(rc, "shd_route_hops")
         return hops, mx
 
+    def ties(self, sources, targets, dispatch: bool = True):
+        """shd_route_ties: (count, rel_lo, rel_hi) of every (source, target) entry: the number
+        of shortest paths (uint64, saturating at 2^64 - 1) and the smallest and largest
+        reliability any of them has.  Failed entries are (0, NaN, NaN); a missing self-loop or
+        an unreachable target raises RouteError with ``err.partial`` = the arrays."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        cnt = np.empty((len(s), len(t)), np.uint64)
+        lo = np.empty((len(s), len(t))); hi = np.empty((len(s), len(t)))
+        rc = load_library().shd_route_ties(self._h, _p(s), len(s), _p(t), len(t),
+                                           DISPATCH if dispatch else 0, _p(cnt), _p(lo), _p(hi))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_ties")
+            err.partial = (cnt, lo, hi)
+            raise err
+        _check(rc, "shd_route_ties")
+        return cnt, lo, hi
+
     def paths(self, pair_src, pair_tgt, dispatch: bool = True):
         """shd_route_paths: (off, vert, edge) of the explicit routes of the pairs, in the
         caller's order: vert[off[k]:off[k+1]] = pair k's vertices from source to target
@@ -382,6 +405,17 @@ class RouteEngine:
             self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0,
             ptr(d_hops), ptr(d_rowmax), C.c_void_p(stream) if stream else None)
         _check(rc, "shd_route_hops_async")
+
+    def ties_async(self, d_src, d_tgt, d_count, d_rel_lo, d_rel_hi, stream=None, dispatch=True, ld=None):
+        """shd_route_ties_async over device tensors: int32 sources and targets, a 64-bit integer
+        tensor for the counts (unsigned values) and float64 bounds; any output may be None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_ties_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0,
+            ptr(d_count), ptr(d_rel_lo), ptr(d_rel_hi), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_ties_async")
 
     def rows_async(self, d_src, d_tgt, d_lat, d_rel, d_rowmin, stream=None, dispatch=True, ld=None):
         ns, nt = int(d_src.numel()), int(d_tgt.numel())

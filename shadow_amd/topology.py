@@ -31,6 +31,7 @@ EXPORTS = (
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
     "shd_topology_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
+    "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
 VATTRS = ("ip", "citycode", "countrycode", "geocode", "type")  # SHD_VATTR_* order
@@ -42,6 +43,13 @@ class _GraphML(C.Structure):
                 ("bandwidth_down", C.POINTER(C.c_double)), ("bandwidth_up", C.POINTER(C.c_double)),
                 ("has_vertex_packetloss", C.c_int32), ("has_vertex_str", C.c_int32 * 5),
                 ("vertex_str", C.POINTER(C.c_char_p) * 5)]
+
+
+class TieStats(C.Structure):
+    """shd_tie_stats_t (include/shd_topology.h)."""
+    _fields_ = [("pairs", C.c_uint64), ("tied", C.c_uint64), ("sensitive", C.c_uint64), ("saturated", C.c_uint64),
+                ("max_spread", C.c_double), ("worst_src", C.c_int32), ("worst_dst", C.c_int32),
+                ("worst_count", C.c_uint64), ("worst_lo", C.c_double), ("worst_hi", C.c_double)]
 
 
 _lib = None
@@ -110,6 +118,16 @@ def load_library():
     L.shd_topology_link_line.restype = C.c_int64
     L.shd_topology_link_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, I32, I32, I32, D, D,
                                          C.c_uint64, C.c_int]
+    L.shd_topology_tie_stats.restype = C.c_int
+    L.shd_topology_tie_stats.argtypes = [P, C.POINTER(TieStats)]
+    L.shd_topology_dump_ties.restype = C.c_int
+    L.shd_topology_dump_ties.argtypes = [P, P]
+    L.shd_topology_tie_line.restype = C.c_int64
+    L.shd_topology_tie_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, I32, I32, C.c_uint64, D, D,
+                                        C.c_int]
+    L.shd_topology_tie_summary_line.restype = C.c_int64
+    L.shd_topology_tie_summary_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(TieStats),
+                                                C.c_int]
     S = C.c_char_p
     L.shd_attach_create.restype = C.c_int
     L.shd_attach_create.argtypes = [C.POINTER(P), C.POINTER(_GraphML)]
@@ -370,6 +388,20 @@ class Topology:
         """shd_topology_dump_link_loads into the file `path`: one line per edge that carried
         packets."""
         self._dump("dump_link_loads", path)
+
+    def tie_stats(self) -> dict:
+        """shd_topology_tie_stats over the stored off-diagonal pairs: {pairs, tied, sensitive,
+        saturated, max_spread, worst_src, worst_dst, worst_count, worst_lo, worst_hi}."""
+        st = TieStats()
+        rc = load_library().shd_topology_tie_stats(self._h, C.byref(st))
+        if rc:
+            raise RuntimeError(f"tie_stats failed ({rc})")
+        return {k: getattr(st, k) for k, _ in TieStats._fields_}
+
+    def dump_ties(self, path: str):
+        """shd_topology_dump_ties into the file `path`: one line per pair whose reliability
+        depends on the tie rule, then the summary line."""
+        self._dump("dump_ties", path)
 
     def table(self, vertices):
         """Dense lookup(i, j) table (lat, rel) for a vertex list, via the public getters."""
