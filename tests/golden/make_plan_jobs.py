@@ -62,7 +62,52 @@ def _cases():
     return c
 
 
-CASES = _cases()
+def _knob_cases():
+    """The planner knob values no default reaches (tests/test_knobs_gpu.py runs their rows): one
+    case per value, on the graph, rank and base environment where it moves the plan.  The list
+    schedule's costs move a plan only when fewer roots than workgroup slots start at tick 0,
+    hence SHD_ROUTE_SEED_ROOTS beside them; SHD_ROUTE_HOPDEG above its default needs a vertex of
+    more than 256 neighbours (hub300).  name -> (graph, environment, world, rank), and
+    KNOB_OF[name] = the variable the case is about."""
+    c, of = {}, {}
+
+    def add(gname, base, world, rank, knob, value):
+        tag = gname + ("" if world == 1 else f"-w{world}r{rank}")
+        name = f"{tag}-{knob[10:].lower()}{value}"
+        c[name] = (gname, {**base, knob: value}, world, rank)
+        of[name] = knob
+
+    for knob, value in (("SHD_ROUTE_LMSEEDS", "1"), ("SHD_ROUTE_LMSEEDS", "2"), ("SHD_ROUTE_SEEDALPHA", "0"),
+                        ("SHD_ROUTE_SEEDALPHA", "10"), ("SHD_ROUTE_HOPDEG", "1"), ("SHD_ROUTE_SEED_ROOTS", "0"),
+                        ("SHD_ROUTE_SEED_ROOTS", "1"), ("SHD_ROUTE_SEED_ROOTS", "1000000"), ("SHD_ROUTE_STORE_SYNC", "1"),
+                        ("SHD_ROUTE_FLAGAT", "1")):
+        add("ba400", KD7, 1, 0, knob, value)
+    add("hub300", KD7, 1, 0, "SHD_ROUTE_HOPDEG", "100000")
+    for knob, value in (("SHD_ROUTE_TOPCAP", "1"), ("SHD_ROUTE_TOPCAP", "64")):
+        add("ba400", KD7, 3, 1, knob, value)
+    for knob, value in (("SHD_ROUTE_ROOTCOST", "0.1"), ("SHD_ROUTE_ROOTCOST", "50"), ("SHD_ROUTE_FLAGAT", "0")):
+        add("ba400", {**KD7, "SHD_ROUTE_SEED_ROOTS": "0"}, 1, 0, knob, value)     # one unseeded root
+    for knob, value in (("SHD_ROUTE_LMCOST", "0.1"), ("SHD_ROUTE_LMCOST", "50")):
+        add("ba400", {**KD7, "SHD_ROUTE_SEED_ROOTS": "1"}, 1, 0, knob, value)     # one landmark-seeded root
+    for knob, value in (("SHD_ROUTE_LMSPREAD", "0"), ("SHD_ROUTE_LMALL_SMALL", "0")):
+        add("lmonly3000", KD, 1, 0, knob, value)
+    return c, of
+
+
+KNOB_CASES, KNOB_OF = _knob_cases()
+CASES = {**_cases(), **KNOB_CASES}
+
+
+def _hub300():
+    """shape_graphs.star(300) with a self-loop on every vertex: the hub has 299 neighbours, more
+    than the default SHD_ROUTE_HOPDEG lets a two-hop seed pass through."""
+    import dataclasses
+    from tests import shape_graphs
+    g = shape_graphs.star(300)
+    lv = np.setdiff1d(np.arange(g.n), g.src[g.src == g.dst]).astype(np.int32)
+    return dataclasses.replace(g, src=np.concatenate([g.src, lv]), dst=np.concatenate([g.dst, lv]),
+                               latency=np.concatenate([g.latency, np.full(len(lv), 2.0)]),
+                               packetloss=np.concatenate([g.packetloss, np.zeros(len(lv))]), name="hub300")
 
 
 def graph(name):
@@ -72,6 +117,8 @@ def graph(name):
         return internet_like(300, 2, seed=340, name="ba300")
     if name == "lmonly3000":
         return internet_like(3000, 3, seed=77, name="ba3000")
+    if name == "hub300":
+        return _hub300()
     return _graph(name)
 
 

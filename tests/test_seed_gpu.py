@@ -505,50 +505,60 @@ def test_landmark_only_plans(oracle_mod, monkeypatch, world, vloss):
     og = oracle_mod.OracleGraph(g)
     seen = []
     for r in range(world):
-        plan = eng.plan(T, world, r)
-        info = dict(plan.info)
-        assert info["seeded"] == 1 and info["levels"] == 1 and info["helpers"] == 0 and info["stored_rows"] == 0, info
-        lat, rel, mn = _plan_rows(eng, plan, T)
-        pos = plan.positions.copy()
-        olat, orel, _, _ = og.source_rows(T[pos], T, oracle_mod.TIE_MINKEY)
-        assert np.array_equal(lat, olat) and np.array_equal(mn, olat.min(axis=1))
-        if vloss:
-            # vertex factors: the walks fold from (1.0 * f_s) * f_t, the reference's order
-            # (topology.c:1443-1462, then :1499): bit-exact against the oracle, and against
-            # the engine's unseeded rows
-            assert np.array_equal(rel, orel, equal_nan=True)
-            monkeypatch.setenv("SHD_ROUTE_SEED", "0")
-            _, rel0, _ = route.RouteEngine(g).rows(T[pos][::7], T, dispatch=False)
-            monkeypatch.delenv("SHD_ROUTE_SEED")
-            assert np.array_equal(rel[::7], rel0)
-        else:
-            assert np.array_equal(rel, orel)
-        seen.extend(pos.tolist())
-        # the device-built plan (default) recomputes its landmark rows, queue order and jobs
-        # in every rows call (round 6: four launches); reusing the last refresh, or refreshing
-        # explicitly first, gives the same rows
-        assert info["launches"] == 4 and info["store_bytes"] > 0, info
-        lat_r, rel_r, _ = _plan_rows(eng, plan, T, reuse=True)
-        assert np.array_equal(lat_r, lat) and np.array_equal(rel_r, rel, equal_nan=True)
-        plan.refresh_async()
-        lat_r, rel_r, _ = _plan_rows(eng, plan, T, reuse=True)
-        assert np.array_equal(lat_r, lat) and np.array_equal(rel_r, rel, equal_nan=True)
-        plan.close()
-        # the host builds (host seeds, or device seeds with host jobs) take the landmark rows
-        # computed when the plan is made into their own store
-        for knob in ("SHD_ROUTE_GPUCHOICE", "SHD_ROUTE_PLANDEV"):
-            monkeypatch.setenv(knob, "0")
-            plan = eng.plan(T, world, r)
-            i2 = dict(plan.info)
-            skip = ("store_bytes", "launches")
-            assert i2["launches"] == 1 and i2["store_bytes"] > 0, (knob, i2)
-            assert {k: v for k, v in i2.items() if k not in skip} == {k: v for k, v in info.items() if k not in skip}, (knob, i2)
-            assert np.array_equal(plan.positions, pos)
-            lat2, rel2, _ = _plan_rows(eng, plan, T)
-            assert np.array_equal(lat2, lat) and np.array_equal(rel2, rel)
-            plan.close()
-            monkeypatch.delenv(knob)
+        seen.extend(check_landmark_only_rank(oracle_mod, monkeypatch, eng, og, world, r, vloss))
     assert sorted(seen) == list(range(len(T)))
+
+
+def check_landmark_only_rank(oracle_mod, monkeypatch, eng, og, world, r, vloss=False):
+    """Rank r's landmark-only plan of all vertices of eng's graph, as test_landmark_only_plans
+    states it; returns the rank's positions.  (Also run by tests/test_knobs_gpu.py with the hub
+    rows in the context's own 256-thread block.)"""
+    from shadow_amd import route
+    g = eng.graph
+    T = g.targets()
+    plan = eng.plan(T, world, r)
+    info = dict(plan.info)
+    assert info["seeded"] == 1 and info["levels"] == 1 and info["helpers"] == 0 and info["stored_rows"] == 0, info
+    lat, rel, mn = _plan_rows(eng, plan, T)
+    pos = plan.positions.copy()
+    olat, orel, _, _ = og.source_rows(T[pos], T, oracle_mod.TIE_MINKEY)
+    assert np.array_equal(lat, olat) and np.array_equal(mn, olat.min(axis=1))
+    if vloss:
+        # vertex factors: the walks fold from (1.0 * f_s) * f_t, the reference's order
+        # (topology.c:1443-1462, then :1499): bit-exact against the oracle, and against
+        # the engine's unseeded rows
+        assert np.array_equal(rel, orel, equal_nan=True)
+        monkeypatch.setenv("SHD_ROUTE_SEED", "0")
+        _, rel0, _ = route.RouteEngine(g).rows(T[pos][::7], T, dispatch=False)
+        monkeypatch.delenv("SHD_ROUTE_SEED")
+        assert np.array_equal(rel[::7], rel0)
+    else:
+        assert np.array_equal(rel, orel)
+    # the device-built plan (default) recomputes its landmark rows, queue order and jobs
+    # in every rows call (round 6: four launches); reusing the last refresh, or refreshing
+    # explicitly first, gives the same rows
+    assert info["launches"] == 4 and info["store_bytes"] > 0, info
+    lat_r, rel_r, _ = _plan_rows(eng, plan, T, reuse=True)
+    assert np.array_equal(lat_r, lat) and np.array_equal(rel_r, rel, equal_nan=True)
+    plan.refresh_async()
+    lat_r, rel_r, _ = _plan_rows(eng, plan, T, reuse=True)
+    assert np.array_equal(lat_r, lat) and np.array_equal(rel_r, rel, equal_nan=True)
+    plan.close()
+    # the host builds (host seeds, or device seeds with host jobs) take the landmark rows
+    # computed when the plan is made into their own store
+    for knob in ("SHD_ROUTE_GPUCHOICE", "SHD_ROUTE_PLANDEV"):
+        monkeypatch.setenv(knob, "0")
+        plan = eng.plan(T, world, r)
+        i2 = dict(plan.info)
+        skip = ("store_bytes", "launches")
+        assert i2["launches"] == 1 and i2["store_bytes"] > 0, (knob, i2)
+        assert {k: v for k, v in i2.items() if k not in skip} == {k: v for k, v in info.items() if k not in skip}, (knob, i2)
+        assert np.array_equal(plan.positions, pos)
+        lat2, rel2, _ = _plan_rows(eng, plan, T)
+        assert np.array_equal(lat2, lat) and np.array_equal(rel2, rel)
+        plan.close()
+        monkeypatch.delenv(knob)
+    return pos.tolist()
 
 
 @pytest.mark.parametrize("lm2", ["64", "256"])
