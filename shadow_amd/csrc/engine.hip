@@ -1,5 +1,8 @@
-// engine.hip -- host side of the routing engine (C-ABI in include/shd_route.h); the seeded-row
-// planner (shd_route_plan_*) is plan.hpp, included below once its prerequisites are defined.
+// engine.hip -- host side of the routing engine (C-ABI in include/shd_route.h): creation,
+// selection, the rows, K4, the fill, host memory and the stats.  The seeded-row planner
+// (shd_route_plan_*) is plan.hpp and the path calls (hops, link loads, tie envelope) are
+// path_calls.hpp over the host-only stages of path_host.hpp, both included below once their
+// prerequisites are defined.
 #include "common.hpp"
 
 #include <array>
@@ -26,6 +29,7 @@
 #include "path_ties.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
+#include "path_host.hpp"
 
 using namespace shd;
 
@@ -147,21 +151,7 @@ struct shd_route {
     int fw_nrtab = 0;
     size_t fwkey_cap = 0;
     int fw_np = 0, fw_ready = 0;
-    // path hops (path_hops.hpp): the in-CSR with edge ids (built at the first hops call), the
-    // workgroup slices of the HBM pointer jumping and the row scratch, grown on demand
-    int hp_ready = 0, hp_slots = 0;
-    int* d_hp_row = nullptr; int* d_hp_col = nullptr; int* d_hp_eid = nullptr; double* d_hp_w = nullptr;
-    int* d_hp_self = nullptr; int* d_hp_ident = nullptr; int* d_hp_saved = nullptr;
-    char* d_hp_ws = nullptr; size_t hp_ws_stride = 0;
-    char* d_hp_buf = nullptr; size_t hp_buf_cap = 0;
-    // link loads (link_loads.hpp): the workgroup slices of the tree sums' HBM form
-    int ld_ready = 0;
-    char* d_ld_ws = nullptr; size_t ld_ws_cap = 0;
-    // tie envelope (path_ties.hpp): per-in-arc reliabilities aligned with the hops in-CSR and the
-    // out-CSR of the release pass (built at the first ties call), the HBM form's workgroup slices
-    int ti_ready = 0;
-    double* d_ti_r = nullptr; int* d_ti_row = nullptr; int* d_ti_head = nullptr; double* d_ti_w = nullptr;
-    char* d_ti_ws = nullptr; size_t ti_ws_cap = 0;
+    PathDev path;  // hops, link loads and tie envelope (path_calls.hpp)
     uint64_t device_bytes = 0;
     // host copies needed for lazy dense build
     std::vector<int32_t> e_src, e_dst;
@@ -172,6 +162,7 @@ struct shd_route {
 namespace {
 
 HostPool* host_pool();  // (plan.hpp; shd_route_create starts the planner's workers)
+void path_free(PathDev& p);  // (path_calls.hpp; shd_route_destroy frees the path calls' buffers)
 
 int hip_check(hipError_t e) { return e == hipSuccess ? SHD_ROUTE_OK : SHD_ROUTE_EDEVICE; }
 
@@ -596,10 +587,7 @@ void shd_route_destroy(shd_route_t* c) {
     if (c->d_lm_drow) (void)hipFree(c->d_lm_drow);
     if (c->d_lm_prow) (void)hipFree(c->d_lm_prow);
     if (c->d_hub_ws) (void)hipFree(c->d_hub_ws);
-    if (c->d_hp_ws) (void)hipFree(c->d_hp_ws);
-    if (c->d_hp_buf) (void)hipFree(c->d_hp_buf);
-    if (c->d_ld_ws) (void)hipFree(c->d_ld_ws);
-    if (c->d_ti_ws) (void)hipFree(c->d_ti_ws);
+    path_free(c->path);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
 }
@@ -689,6 +677,13 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     int alloc(size_t b) { return hipMalloc(&p, b ? b : 1) == hipSuccess ? SHD_ROUTE_OK : SHD_ROUTE_ENOMEM; }
 };
+}  // namespace
+
+// hops, link loads and the tie envelope: shd_route_hops*, _paths, _loads*, _pair_loads, _ties*
+// (and the stages every blocking call shares, host_rows below among them: SoftCode, host_chunk)
+#include "path_calls.hpp"
+
+namespace {
 
 // Host-pointer wrapper: chunks rows so device output stays bounded, copies back.
 template <typename Launch>
@@ -698,7 +693,7 @@ int host_rows(shd_route* c, const int32_t* src, int32_t ns, const int32_t* tgt, 
     if (ns == 0) return SHD_ROUTE_OK;
     if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
     const size_t row_bytes = sizeof(double) * (size_t)std::max(nt, 1);
-    int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / row_bytes));
+    const int32_t chunk = host_chunk(ns, row_bytes);
     DevBuf dsrc, dtgt, dlat, drel, dmin;
     int rc;
     if ((rc = dsrc.alloc(sizeof(int32_t) * chunk)) || (rc = dtgt.alloc(sizeof(int32_t) * std::max(nt, 1))) ||
@@ -707,7 +702,7 @@ int host_rows(shd_route* c, const int32_t* src, int32_t ns, const int32_t* tgt, 
         return rc;
     if (nt && hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess)
         return SHD_ROUTE_EDEVICE;
-    int soft = SHD_ROUTE_OK;
+    SoftCode sc;
     for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
         int32_t k = std::min(chunk, ns - i0);
         if (hipMemcpy(dsrc.p, src + i0, sizeof(int32_t) * k, hipMemcpyHostToDevice) != hipSuccess)
@@ -717,8 +712,7 @@ int host_rows(shd_route* c, const int32_t* src, int32_t ns, const int32_t* tgt, 
         if (rc) return rc;
         // per-entry failures (missing self-loop, unreachable target) leave NaN in those
         // entries only: the rows are still copied out and the code returned at the end
-        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
-        if (rc && !soft) soft = rc;
+        if ((rc = sc.sync(c))) return rc;
         if (lat_out && hipMemcpy(lat_out + (size_t)i0 * nt, dlat.p, row_bytes * k, hipMemcpyDeviceToHost) != hipSuccess)
             return SHD_ROUTE_EDEVICE;
         if (rel_out && hipMemcpy(rel_out + (size_t)i0 * nt, drel.p, row_bytes * k, hipMemcpyDeviceToHost) != hipSuccess)
@@ -726,7 +720,7 @@ int host_rows(shd_route* c, const int32_t* src, int32_t ns, const int32_t* tgt, 
         if (row_min_out && hipMemcpy(row_min_out + i0, dmin.p, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess)
             return SHD_ROUTE_EDEVICE;
     }
-    return soft;
+    return sc.soft;
 }
 }  // namespace
 
@@ -1431,777 +1425,6 @@ int shd_route_fill_triangle(shd_route_t* c, const int32_t* A, int32_t na, int32_
         *min_out = mb == ~0ull ? INFINITY : m;
     }
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return soft;
-}
-
-}  // extern "C"
-
-// =============================================================================
-// Path hops (path_hops.hpp): hop counts and explicit routes of the chosen paths
-// =============================================================================
-namespace {
-
-// the in-CSR with edge ids, rows sorted by (tail, edge id), and each vertex's self-loop edge
-int ensure_hops(shd_route* c) {
-    if (c->hp_ready) return SHD_ROUTE_OK;
-    const int n = c->n;
-    std::vector<int> head, tail, eid, self(n, -1);
-    for (int e = 0; e < c->m; e++) {
-        const int a = c->e_src[e], b = c->e_dst[e];
-        if (a == b) {
-            if (self[a] < 0) self[a] = e;
-            continue;
-        }
-        head.push_back(b); tail.push_back(a); eid.push_back(e);
-        if (!c->directed) { head.push_back(a); tail.push_back(b); eid.push_back(e); }
-    }
-    const size_t k = head.size();
-    std::vector<size_t> idx(k);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-        if (head[x] != head[y]) return head[x] < head[y];
-        if (tail[x] != tail[y]) return tail[x] < tail[y];
-        return eid[x] < eid[y];
-    });
-    std::vector<int> row(n + 1, 0), col(k), ed(k), ident(n);
-    std::vector<double> w(k);
-    for (size_t q = 0; q < k; q++) {
-        const size_t a = idx[q];
-        row[head[a] + 1]++;
-        col[q] = tail[a];
-        ed[q] = eid[a];
-        w[q] = c->e_lat[eid[a]];
-    }
-    for (int v = 0; v < n; v++) row[v + 1] += row[v];
-    std::iota(ident.begin(), ident.end(), 0);
-    std::vector<int> z(1, 0);
-    int rc = upload(c, &c->d_hp_row, row);
-    if (!rc) rc = upload(c, &c->d_hp_col, col);
-    if (!rc) rc = upload(c, &c->d_hp_eid, ed);
-    if (!rc) rc = upload(c, &c->d_hp_w, w);
-    if (!rc) rc = upload(c, &c->d_hp_self, self);
-    if (!rc) rc = upload(c, &c->d_hp_ident, ident);
-    if (!rc) rc = upload(c, &c->d_hp_saved, z);
-    if (!rc && n <= 65535 && kHpSmall + hp_state_bytes<uint16_t>(n) <= kLdsBudget)
-        rc = hip_check(hipFuncSetAttribute((const void*)hops_depth_kernel<uint16_t, true, 1024>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(kHpSmall + hp_state_bytes<uint16_t>(n))));
-    if (rc) return rc;
-    c->hp_ready = 1;
-    return SHD_ROUTE_OK;
-}
-
-DevHops dev_hops(const shd_route* c) {
-    DevHops g;
-    g.n = c->n; g.row_in = c->d_hp_row; g.col_in = c->d_hp_col; g.eid_in = c->d_hp_eid; g.w_in = c->d_hp_w;
-    g.self_eid = c->d_hp_self;
-    return g;
-}
-
-// scratch budget of the hops calls' distance and parent rows (bytes)
-size_t hp_budget() {
-    if (const char* e = getenv("SHD_ROUTE_HOPS_SCRATCH")) {
-        const unsigned long long b = strtoull(e, nullptr, 10);
-        if (b > 0) return (size_t)b;
-    }
-    return (size_t)1 << 30;
-}
-
-int hp_scratch(shd_route* c, size_t bytes) {
-    if (bytes <= c->hp_buf_cap) return SHD_ROUTE_OK;
-    if (c->d_hp_buf) (void)hipFree(c->d_hp_buf);
-    c->d_hp_buf = nullptr;
-    c->hp_buf_cap = 0;
-    if (hipMalloc((void**)&c->d_hp_buf, bytes) != hipSuccess) return SHD_ROUTE_ENOMEM;
-    c->hp_buf_cap = bytes;
-    return SHD_ROUTE_OK;
-}
-
-// dist (k x n f64) = the all-vertex latency rows of the sources, par (k x n u32) their parent arcs
-int hp_rows(shd_route* c, const int32_t* d_src, int k, double* dist, uint32_t* par, hipStream_t st) {
-    const int n = c->n;
-    hipLaunchKernelGGL(hops_err_park_kernel, dim3(1), dim3(1), 0, st, c->d_err, c->d_hp_saved);
-    int rc = shd_route_rows_async(c, d_src, k, c->d_hp_ident, n, n, 0u, dist, nullptr, nullptr, st);
-    hipLaunchKernelGGL(hops_err_unpark_kernel, dim3(1), dim3(1), 0, st, c->d_err, (const int*)c->d_hp_saved);
-    if (rc) return rc;
-    const dim3 grid((unsigned)std::min((n + 255) / 256, 4096), (unsigned)std::min(k, 65535));
-    hipLaunchKernelGGL(hops_parent_kernel<256>, grid, dim3(256), 0, st, dev_hops(c), (const double*)dist,
-                       (long long)n, d_src, k, par, (long long)n, c->d_err);
-    return hip_check(hipGetLastError());
-}
-
-// the hop rows of k sources from their parent rows (hops_depth_kernel), LDS or HBM state
-int hp_depth(shd_route* c, const uint32_t* par, const int32_t* d_src, int k, const int32_t* d_tgt, int nt,
-             long long ld, int mode, int quiet, int32_t* d_hops, int32_t* d_row_max, hipStream_t st) {
-    const int n = c->n;
-    const DevHops g = dev_hops(c);
-    const char* e = getenv("SHD_ROUTE_HOPS_LDS");  // "0": the HBM form on graphs the LDS form takes
-    const bool lds = mode != 2 && n <= 65535 && kHpSmall + hp_state_bytes<uint16_t>(n) <= kLdsBudget &&
-                     !(e && *e && atoi(e) == 0);
-    if (lds) {
-        hipLaunchKernelGGL((hops_depth_kernel<uint16_t, true, 1024>), dim3(std::min(k, 1024)), dim3(1024),
-                           kHpSmall + hp_state_bytes<uint16_t>(n), st, g, par, (long long)n, d_src, k, d_tgt, nt, ld,
-                           mode, quiet, d_hops, d_row_max, (char*)nullptr, (size_t)0, c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    const bool small = n <= 65535;
-    if (mode != 2 && !c->d_hp_ws) {
-        c->hp_ws_stride = a16(small ? hp_state_bytes<uint16_t>(n) : hp_state_bytes<uint32_t>(n));
-        c->hp_slots = (int)std::max<size_t>(16, std::min<size_t>(512, ((size_t)256 << 20) / c->hp_ws_stride));
-        if (hipMalloc((void**)&c->d_hp_ws, c->hp_ws_stride * (size_t)c->hp_slots) != hipSuccess) {
-            c->d_hp_ws = nullptr;
-            return SHD_ROUTE_ENOMEM;
-        }
-    }
-    const int grid = std::min(k, mode == 2 ? 1024 : c->hp_slots);
-    if (small)
-        hipLaunchKernelGGL((hops_depth_kernel<uint16_t, false, 1024>), dim3(grid), dim3(1024), kHpSmall, st, g, par,
-                           (long long)n, d_src, k, d_tgt, nt, ld, mode, quiet, d_hops, d_row_max, c->d_hp_ws,
-                           c->hp_ws_stride, c->d_err);
-    else
-        hipLaunchKernelGGL((hops_depth_kernel<uint32_t, false, 1024>), dim3(grid), dim3(1024), kHpSmall, st, g, par,
-                           (long long)n, d_src, k, d_tgt, nt, ld, mode, quiet, d_hops, d_row_max, c->d_hp_ws,
-                           c->hp_ws_stride, c->d_err);
-    return hip_check(hipGetLastError());
-}
-
-int hp_mode(const shd_route* c, uint32_t flags) {
-    if (!(flags & SHD_ROUTE_DISPATCH)) return 0;
-    return c->complete ? 2 : c->prefer_direct ? 1 : 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int shd_route_hops_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
-                         int64_t ld, uint32_t flags, int32_t* d_hops, int32_t* d_row_max, void* stream) {
-    if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
-    if (ns == 0) return SHD_ROUTE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    int rc = ensure_hops(c);
-    if (rc) return rc;
-    const int mode = hp_mode(c, flags);
-    if (mode == 2) return hp_depth(c, nullptr, d_src, ns, d_tgt, nt, (long long)ld, 2, 0, d_hops, d_row_max, st);
-    const size_t per = (size_t)c->n * (sizeof(double) + sizeof(uint32_t));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)ns, hp_budget() / per));
-    if ((rc = hp_scratch(c, per * (size_t)chunk))) return rc;
-    double* dist = (double*)c->d_hp_buf;
-    uint32_t* par = (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)c->n * (size_t)chunk);
-    for (int i0 = 0; i0 < ns; i0 += chunk) {
-        const int k = std::min(chunk, ns - i0);
-        if ((rc = hp_rows(c, d_src + i0, k, dist, par, st))) return rc;
-        if ((rc = hp_depth(c, par, d_src + i0, k, d_tgt, nt, (long long)ld, mode, 0,
-                           d_hops ? d_hops + (long long)i0 * ld : nullptr, d_row_max ? d_row_max + i0 : nullptr, st)))
-            return rc;
-    }
-    return SHD_ROUTE_OK;
-}
-
-int shd_route_hops(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
-                   int32_t* hops_out, int32_t* row_max_out) {
-    if (!c || ns < 0 || nt < 0 || (ns && !src) || (nt && !tgt)) return SHD_ROUTE_EINVAL;
-    if (ns == 0) return SHD_ROUTE_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    const size_t row_bytes = sizeof(int32_t) * (size_t)std::max(nt, 1);
-    const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / row_bytes));
-    DevBuf dsrc, dtgt, dh, dm;
-    int rc;
-    if ((rc = dsrc.alloc(sizeof(int32_t) * ns)) || (rc = dtgt.alloc(sizeof(int32_t) * std::max(nt, 1))) ||
-        (rc = dh.alloc(row_bytes * chunk)) || (rc = dm.alloc(sizeof(int32_t) * chunk)))
-        return rc;
-    if (hipMemcpy(dsrc.p, src, sizeof(int32_t) * ns, hipMemcpyHostToDevice) != hipSuccess ||
-        (nt && hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess))
-        return SHD_ROUTE_EDEVICE;
-    int soft = SHD_ROUTE_OK;
-    for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
-        const int32_t k = std::min(chunk, ns - i0);
-        rc = shd_route_hops_async(c, (const int32_t*)dsrc.p + i0, k, (const int32_t*)dtgt.p, nt, nt, flags,
-                                  (int32_t*)dh.p, (int32_t*)dm.p, nullptr);
-        if (rc) return rc;
-        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
-        if (rc && !soft) soft = rc;
-        if (hops_out && nt &&
-            hipMemcpy(hops_out + (size_t)i0 * nt, dh.p, sizeof(int32_t) * (size_t)nt * k, hipMemcpyDeviceToHost) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        if (row_max_out && hipMemcpy(row_max_out + i0, dm.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-    }
-    return soft;
-}
-
-int shd_route_paths(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs, uint32_t flags,
-                    int64_t* off_out, int32_t* vert_out, int32_t* edge_out, int64_t cap) {
-    if (!c || npairs < 0 || npairs > 0x7FFFFFFF || (npairs && (!pair_src || !pair_tgt)) || !off_out || cap < 0 ||
-        (cap > 0 && (!vert_out || !edge_out)))
-        return SHD_ROUTE_EINVAL;
-    off_out[0] = 0;
-    if (npairs == 0) return SHD_ROUTE_OK;
-    const int n = c->n;
-    const int np = (int)npairs;
-    for (int k = 0; k < np; k++)
-        if (pair_src[k] < 0 || pair_src[k] >= n || pair_tgt[k] < 0 || pair_tgt[k] >= n) return SHD_ROUTE_EINVAL;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    int rc = ensure_hops(c);
-    if (rc) return rc;
-    const int mode = hp_mode(c, flags);
-    const bool want = vert_out != nullptr && cap > 0;
-    // pairs grouped by source (any order, repeats allowed): order[g] = the caller's pair at
-    // grouped position g; us = the distinct sources, first[u] = the first grouped pair of us[u]
-    std::vector<int> order(np);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pair_src[a] < pair_src[b]; });
-    std::vector<int32_t> us, gsi(np), gt(np);
-    std::vector<int> first;
-    for (int g = 0; g < np; g++) {
-        const int32_t s = pair_src[order[g]];
-        if (us.empty() || us.back() != s) { us.push_back(s); first.push_back(g); }
-        gsi[g] = (int32_t)us.size() - 1;
-        gt[g] = pair_tgt[order[g]];
-    }
-    const int nu = (int)us.size();
-    first.push_back(np);
-    // sources per chunk: distance, parent and hop rows within the scratch budget
-    const size_t per = (size_t)n * (sizeof(double) + sizeof(uint32_t) + sizeof(int32_t));
-    const int chunk = mode == 2 ? nu : (int)std::max<size_t>(1, std::min<size_t>((size_t)nu, hp_budget() / per));
-    if (mode != 2 && (rc = hp_scratch(c, per * (size_t)chunk))) return rc;
-    double* dist = (double*)c->d_hp_buf;
-    uint32_t* par = mode == 2 ? nullptr : (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)n * (size_t)chunk);
-    int32_t* hrow = mode == 2 ? nullptr
-                              : (int32_t*)(c->d_hp_buf + (sizeof(double) + sizeof(uint32_t)) * (size_t)n * (size_t)chunk);
-    std::vector<int32_t> gcnt(np, -1);       // hop count of each grouped pair
-    std::vector<int64_t> gvo(np, 0), geo(np, 0);  // its place in the staged vertices / edges
-    std::vector<int32_t> sv, se;             // paths staged in grouped order
-    int soft = SHD_ROUTE_OK;
-    const DevHops g = dev_hops(c);
-    for (int u0 = 0; u0 < nu; u0 += chunk) {
-        const int k = std::min(chunk, nu - u0);
-        const int g0 = first[u0], g1 = first[u0 + k], cp = g1 - g0;
-        DevBuf dsrc, dsi, dtg, dcnt;
-        if ((rc = dsrc.alloc(sizeof(int32_t) * k)) || (rc = dsi.alloc(sizeof(int32_t) * cp)) ||
-            (rc = dtg.alloc(sizeof(int32_t) * cp)) || (rc = dcnt.alloc(sizeof(int32_t) * cp)))
-            return rc;
-        std::vector<int32_t> lsi(cp);
-        for (int q = 0; q < cp; q++) lsi[q] = gsi[g0 + q] - u0;
-        if (hipMemcpy(dsrc.p, us.data() + u0, sizeof(int32_t) * k, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dsi.p, lsi.data(), sizeof(int32_t) * cp, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dtg.p, gt.data() + g0, sizeof(int32_t) * cp, hipMemcpyHostToDevice) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        if (mode != 2) {
-            if ((rc = hp_rows(c, (const int32_t*)dsrc.p, k, dist, par, nullptr))) return rc;
-            if ((rc = hp_depth(c, par, (const int32_t*)dsrc.p, k, c->d_hp_ident, n, (long long)n, 0, 1, hrow, nullptr,
-                               nullptr)))
-                return rc;
-        }
-        const int pgrid = std::min((cp + 255) / 256, 4096);
-        hipLaunchKernelGGL(hops_pairs_kernel, dim3(pgrid), dim3(256), 0, nullptr, g, (const int*)dsrc.p,
-                           (const int*)dsi.p, (const int*)dtg.p, cp, mode, (const int*)hrow, (int*)dcnt.p, c->d_err);
-        if ((rc = hip_check(hipGetLastError()))) return rc;
-        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
-        if (rc && !soft) soft = rc;
-        if (hipMemcpy(gcnt.data() + g0, dcnt.p, sizeof(int32_t) * cp, hipMemcpyDeviceToHost) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        if (!want) continue;
-        // this chunk's paths, packed in grouped order behind the chunks before it
-        std::vector<long long> lvo(cp), leo(cp);
-        long long tv = 0, te = 0;
-        for (int q = 0; q < cp; q++) {
-            lvo[q] = tv; leo[q] = te;
-            gvo[g0 + q] = (int64_t)sv.size() + tv;
-            geo[g0 + q] = (int64_t)se.size() + te;
-            if (gcnt[g0 + q] >= 0) { tv += gcnt[g0 + q] + 1; te += gcnt[g0 + q]; }
-        }
-        if (tv == 0) continue;
-        DevBuf dvo, deo, dv, de;
-        if ((rc = dvo.alloc(sizeof(long long) * cp)) || (rc = deo.alloc(sizeof(long long) * cp)) ||
-            (rc = dv.alloc(sizeof(int32_t) * (size_t)tv)) || (rc = de.alloc(sizeof(int32_t) * (size_t)std::max(te, 1LL))))
-            return rc;
-        if (hipMemcpy(dvo.p, lvo.data(), sizeof(long long) * cp, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(deo.p, leo.data(), sizeof(long long) * cp, hipMemcpyHostToDevice) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        hipLaunchKernelGGL(hops_extract_kernel, dim3(pgrid), dim3(256), 0, nullptr, g, (const uint32_t*)par,
-                           (long long)n, (const int*)dsrc.p, (const int*)dsi.p, (const int*)dtg.p, (const int*)dcnt.p,
-                           (const long long*)dvo.p, (const long long*)deo.p, cp, mode, (int*)dv.p, (int*)de.p, c->d_err);
-        if ((rc = hip_check(hipGetLastError()))) return rc;
-        if ((rc = shd_route_sync(c, nullptr))) return rc;
-        const size_t v0 = sv.size(), e0 = se.size();
-        sv.resize(v0 + (size_t)tv);
-        se.resize(e0 + (size_t)te);
-        if (hipMemcpy(sv.data() + v0, dv.p, sizeof(int32_t) * (size_t)tv, hipMemcpyDeviceToHost) != hipSuccess ||
-            (te && hipMemcpy(se.data() + e0, de.p, sizeof(int32_t) * (size_t)te, hipMemcpyDeviceToHost) != hipSuccess))
-            return SHD_ROUTE_EDEVICE;
-    }
-    // offsets in the caller's pair order; a failed pair takes no room
-    std::vector<int> gpos(np);
-    for (int gq = 0; gq < np; gq++) gpos[order[gq]] = gq;
-    for (int k = 0; k < np; k++) {
-        const int32_t h = gcnt[gpos[k]];
-        off_out[k + 1] = off_out[k] + (h >= 0 ? h + 1 : 0);
-    }
-    if (off_out[np] > cap) return SHD_ROUTE_EINVAL;
-    int64_t done = 0;  // pairs before k that did not fail: their edges take one slot less each
-    for (int k = 0; k < np; k++) {
-        const int gq = gpos[k];
-        const int32_t h = gcnt[gq];
-        if (h < 0) continue;
-        std::memcpy(vert_out + off_out[k], sv.data() + gvo[gq], sizeof(int32_t) * (size_t)(h + 1));
-        std::memcpy(edge_out + (off_out[k] - done), se.data() + geo[gq], sizeof(int32_t) * (size_t)h);
-        done++;
-    }
-    return soft;
-}
-
-}  // extern "C"
-
-// =============================================================================
-// Link loads (link_loads.hpp): per-edge and per-vertex weight of the chosen paths
-// =============================================================================
-namespace {
-
-// the tree sums of k sources (loads_tree_kernel), state in LDS or in HBM slices
-int ld_tree(shd_route* c, const uint32_t* par, const int32_t* hrow, const int32_t* d_src, int k,
-            const int32_t* d_tgt, int nt, long long ld, const long long* d_eoff, const uint64_t* d_wt, int mode,
-            uint64_t* d_edge, uint64_t* d_transit, uint64_t* d_unrouted, hipStream_t st) {
-    const int n = c->n;
-    const DevHops g = dev_hops(c);
-    auto* wt = (const unsigned long long*)d_wt;
-    auto* el = (unsigned long long*)d_edge;
-    auto* tr = (unsigned long long*)d_transit;
-    auto* un = (unsigned long long*)d_unrouted;
-    if (mode == 2) {  // no tree, no state
-        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, false, 1024>), dim3(std::min(k, 1024)), dim3(1024), kLdSmall,
-                           st, g, par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, (char*)nullptr,
-                           (size_t)0, c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    const size_t lds_bytes = kLdSmall + ld_state_bytes<uint16_t>(n);
-    const bool fits = n <= 65535 && lds_bytes <= kLdsBudget;
-    if (fits && !c->ld_ready) {
-        int rc = hip_check(hipFuncSetAttribute((const void*)loads_tree_kernel<uint16_t, true, 1024>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-        if (rc) return rc;
-        c->ld_ready = 1;
-    }
-    const char* e = getenv("SHD_ROUTE_LOADS_LDS");  // "0": the HBM form on graphs the LDS form takes
-    if (fits && !(e && *e && atoi(e) == 0)) {
-        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, true, 1024>), dim3(std::min(k, 1024)), dim3(1024), lds_bytes,
-                           st, g, par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, (char*)nullptr,
-                           (size_t)0, c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    // HBM slices: a quarter of the hops scratch budget, 16 to 512 workgroup slots
-    const bool small = n <= 65535;
-    const size_t stride = a16(small ? ld_state_bytes<uint16_t>(n) : ld_state_bytes<uint32_t>(n));
-    const int slots = (int)std::max<size_t>(16, std::min<size_t>(512, hp_budget() / 4 / stride));
-    const int grid = std::min(k, slots);
-    if (stride * (size_t)grid > c->ld_ws_cap) {
-        // a launch of this context that still uses the old slices is on the same stream or
-        // synchronised (one rows launch at a time): wait before the slices go
-        if (c->d_ld_ws) {
-            if (hipStreamSynchronize(st) != hipSuccess) return SHD_ROUTE_EDEVICE;
-            (void)hipFree(c->d_ld_ws);
-        }
-        c->d_ld_ws = nullptr;
-        c->ld_ws_cap = 0;
-        if (hipMalloc((void**)&c->d_ld_ws, stride * (size_t)slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
-        c->ld_ws_cap = stride * (size_t)slots;
-    }
-    if (small)
-        hipLaunchKernelGGL((loads_tree_kernel<uint16_t, false, 1024>), dim3(grid), dim3(1024), kLdSmall, st, g, par,
-                           hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, c->d_ld_ws, stride, c->d_err);
-    else
-        hipLaunchKernelGGL((loads_tree_kernel<uint32_t, false, 1024>), dim3(grid), dim3(1024), kLdSmall, st, g, par,
-                           hrow, d_src, k, d_tgt, nt, ld, d_eoff, wt, mode, el, tr, un, c->d_ld_ws, stride, c->d_err);
-    return hip_check(hipGetLastError());
-}
-
-// The loads of ns sources added into the outputs, sources in chunks of the hops scratch:
-// per source a distance row, a parent row and a hop row over all vertices.  Entries: the
-// block (d_eoff null: d_tgt[nt], d_wt row stride ld) or the sparse lists d_eoff gives.
-int ld_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
-               const long long* d_eoff, const uint64_t* d_wt, uint32_t flags, uint64_t* d_edge, uint64_t* d_transit,
-               uint64_t* d_unrouted, hipStream_t st) {
-    int rc = ensure_hops(c);
-    if (rc) return rc;
-    const int n = c->n;
-    const int mode = hp_mode(c, flags);
-    if (mode == 2)
-        return ld_tree(c, nullptr, nullptr, d_src, ns, d_tgt, nt, ld, d_eoff, d_wt, 2, d_edge, d_transit, d_unrouted, st);
-    const size_t per = (size_t)n * (sizeof(double) + sizeof(uint32_t) + sizeof(int32_t));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)ns, hp_budget() / per));
-    if ((rc = hp_scratch(c, per * (size_t)chunk))) return rc;
-    double* dist = (double*)c->d_hp_buf;
-    uint32_t* par = (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)n * (size_t)chunk);
-    int32_t* hrow = (int32_t*)(c->d_hp_buf + (sizeof(double) + sizeof(uint32_t)) * (size_t)n * (size_t)chunk);
-    for (int i0 = 0; i0 < ns; i0 += chunk) {
-        const int k = std::min(chunk, ns - i0);
-        if ((rc = hp_rows(c, d_src + i0, k, dist, par, st))) return rc;
-        if ((rc = hp_depth(c, par, d_src + i0, k, c->d_hp_ident, n, (long long)n, 0, 1, hrow, nullptr, st))) return rc;
-        if ((rc = ld_tree(c, par, hrow, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr,
-                          d_wt && !d_eoff ? d_wt + (long long)i0 * ld : d_wt, mode, d_edge, d_transit, d_unrouted, st)))
-            return rc;
-    }
-    return SHD_ROUTE_OK;
-}
-
-// zero the outputs a call without SHD_ROUTE_LOADS_ADD starts from
-int ld_zero(shd_route* c, uint32_t flags, uint64_t* d_edge, uint64_t* d_transit, uint64_t* d_unrouted, hipStream_t st) {
-    if (flags & SHD_ROUTE_LOADS_ADD) return SHD_ROUTE_OK;
-    if ((d_edge && c->m && hipMemsetAsync(d_edge, 0, sizeof(uint64_t) * (size_t)c->m, st) != hipSuccess) ||
-        (d_transit && hipMemsetAsync(d_transit, 0, sizeof(uint64_t) * (size_t)c->n, st) != hipSuccess) ||
-        (d_unrouted && hipMemsetAsync(d_unrouted, 0, sizeof(uint64_t), st) != hipSuccess))
-        return SHD_ROUTE_EDEVICE;
-    return SHD_ROUTE_OK;
-}
-
-// device accumulators of the blocking calls: zeroed, summed into by every chunk, then copied
-// (or, with SHD_ROUTE_LOADS_ADD, added) into the caller's host arrays
-struct LoadsOut {
-    DevBuf de, dt, du;
-    int m = 0, n = 0;
-    int init(const shd_route* c) {
-        m = c->m; n = c->n;
-        int rc;
-        if ((rc = de.alloc(sizeof(uint64_t) * (size_t)m)) || (rc = dt.alloc(sizeof(uint64_t) * (size_t)n)) ||
-            (rc = du.alloc(sizeof(uint64_t))))
-            return rc;
-        if ((m && hipMemset(de.p, 0, sizeof(uint64_t) * (size_t)m) != hipSuccess) ||
-            hipMemset(dt.p, 0, sizeof(uint64_t) * (size_t)n) != hipSuccess ||
-            hipMemset(du.p, 0, sizeof(uint64_t)) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        return SHD_ROUTE_OK;
-    }
-    static int take(uint64_t* out, const void* dev, size_t count, bool add) {
-        if (!out || !count) return SHD_ROUTE_OK;
-        if (!add) return hipMemcpy(out, dev, sizeof(uint64_t) * count, hipMemcpyDeviceToHost) == hipSuccess
-                             ? SHD_ROUTE_OK : SHD_ROUTE_EDEVICE;
-        std::vector<uint64_t> h(count);
-        if (hipMemcpy(h.data(), dev, sizeof(uint64_t) * count, hipMemcpyDeviceToHost) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        for (size_t q = 0; q < count; q++) out[q] += h[q];
-        return SHD_ROUTE_OK;
-    }
-    int finish(uint32_t flags, uint64_t* edge_out, uint64_t* transit_out, uint64_t* unrouted_out) {
-        const bool add = (flags & SHD_ROUTE_LOADS_ADD) != 0;
-        int rc;
-        if ((rc = take(edge_out, de.p, (size_t)m, add)) || (rc = take(transit_out, dt.p, (size_t)n, add)) ||
-            (rc = take(unrouted_out, du.p, 1, add)))
-            return rc;
-        return SHD_ROUTE_OK;
-    }
-};
-
-// the outputs of a blocking call that has nothing to route
-void ld_host_zero(const shd_route* c, uint32_t flags, uint64_t* edge_out, uint64_t* transit_out, uint64_t* unrouted_out) {
-    if (flags & SHD_ROUTE_LOADS_ADD) return;
-    if (edge_out) std::fill(edge_out, edge_out + c->m, (uint64_t)0);
-    if (transit_out) std::fill(transit_out, transit_out + c->n, (uint64_t)0);
-    if (unrouted_out) *unrouted_out = 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int shd_route_loads_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
-                          int64_t ld, uint32_t flags, const uint64_t* d_wt, uint64_t* d_edge_load, uint64_t* d_transit,
-                          uint64_t* d_unrouted, void* stream) {
-    if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    int rc = ld_zero(c, flags, d_edge_load, d_transit, d_unrouted, st);
-    if (rc || ns == 0 || nt == 0) return rc;
-    return ld_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, d_wt, flags, d_edge_load, d_transit, d_unrouted,
-                      st);
-}
-
-int shd_route_loads(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
-                    const uint64_t* wt, uint64_t* edge_load_out, uint64_t* transit_out, uint64_t* unrouted_out) {
-    if (!c || ns < 0 || nt < 0 || (ns && !src) || (nt && !tgt)) return SHD_ROUTE_EINVAL;
-    for (int32_t i = 0; i < ns; i++)
-        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
-    for (int32_t j = 0; j < nt; j++)
-        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
-    if (ns == 0 || nt == 0) {
-        ld_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
-        return SHD_ROUTE_OK;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    // rows of weights per device chunk: up to 1 GiB
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)nt;
-    const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / row_bytes));
-    DevBuf dsrc, dtgt, dw;
-    LoadsOut out;
-    int rc;
-    if ((rc = dsrc.alloc(sizeof(int32_t) * ns)) || (rc = dtgt.alloc(sizeof(int32_t) * nt)) ||
-        (wt && (rc = dw.alloc(row_bytes * chunk))) || (rc = out.init(c)))
-        return rc;
-    if (hipMemcpy(dsrc.p, src, sizeof(int32_t) * ns, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess)
-        return SHD_ROUTE_EDEVICE;
-    int soft = SHD_ROUTE_OK;
-    for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
-        const int32_t k = std::min(chunk, ns - i0);
-        if (wt && hipMemcpy(dw.p, wt + (size_t)i0 * nt, row_bytes * k, hipMemcpyHostToDevice) != hipSuccess)
-            return SHD_ROUTE_EDEVICE;
-        rc = ld_sources(c, (const int32_t*)dsrc.p + i0, k, (const int32_t*)dtgt.p, nt, nt, nullptr,
-                        wt ? (const uint64_t*)dw.p : nullptr, flags, (uint64_t*)out.de.p, (uint64_t*)out.dt.p,
-                        (uint64_t*)out.du.p, nullptr);
-        if (rc) return rc;
-        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
-        if (rc && !soft) soft = rc;
-    }
-    if ((rc = out.finish(flags, edge_load_out, transit_out, unrouted_out))) return rc;
-    return soft;
-}
-
-int shd_route_pair_loads(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, const uint64_t* pair_wt,
-                         int64_t npairs, uint32_t flags, uint64_t* edge_load_out, uint64_t* transit_out,
-                         uint64_t* unrouted_out) {
-    if (!c || npairs < 0 || npairs > 0x7FFFFFFF || (npairs && (!pair_src || !pair_tgt))) return SHD_ROUTE_EINVAL;
-    const int n = c->n;
-    const int np = (int)npairs;
-    for (int k = 0; k < np; k++)
-        if (pair_src[k] < 0 || pair_src[k] >= n || pair_tgt[k] < 0 || pair_tgt[k] >= n) return SHD_ROUTE_EINVAL;
-    if (np == 0) {
-        ld_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
-        return SHD_ROUTE_OK;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    // pairs grouped by source, as shd_route_paths groups them: the entries of distinct source
-    // u are the grouped positions eoff[u] .. eoff[u + 1]
-    std::vector<int> order(np);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pair_src[a] < pair_src[b]; });
-    std::vector<int32_t> us, gt(np);
-    std::vector<uint64_t> gw(pair_wt ? np : 0);
-    std::vector<long long> eoff;
-    for (int g = 0; g < np; g++) {
-        const int32_t s = pair_src[order[g]];
-        if (us.empty() || us.back() != s) { us.push_back(s); eoff.push_back(g); }
-        gt[g] = pair_tgt[order[g]];
-        if (pair_wt) gw[g] = pair_wt[order[g]];
-    }
-    eoff.push_back(np);
-    const int nu = (int)us.size();
-    DevBuf dsrc, dtgt, dw, doff;
-    LoadsOut out;
-    int rc;
-    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
-        (pair_wt && (rc = dw.alloc(sizeof(uint64_t) * (size_t)np))) ||
-        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) || (rc = out.init(c)))
-        return rc;
-    if (hipMemcpy(dsrc.p, us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dtgt.p, gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
-        (pair_wt && hipMemcpy(dw.p, gw.data(), sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(doff.p, eoff.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess)
-        return SHD_ROUTE_EDEVICE;
-    rc = ld_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, 0, (const long long*)doff.p,
-                    pair_wt ? (const uint64_t*)dw.p : nullptr, flags, (uint64_t*)out.de.p, (uint64_t*)out.dt.p,
-                    (uint64_t*)out.du.p, nullptr);
-    if (rc) return rc;
-    int soft = shd_route_sync(c, nullptr);
-    if (soft && soft != SHD_ROUTE_ENOEDGE && soft != SHD_ROUTE_EUNREACH) return soft;
-    if ((rc = out.finish(flags, edge_load_out, transit_out, unrouted_out))) return rc;
-    return soft;
-}
-
-}  // extern "C"
-
-// =============================================================================
-// Tie envelope (path_ties.hpp): path counts and reliability bounds over tied paths
-// =============================================================================
-namespace {
-
-// the reliabilities of the hops in-CSR's arcs (the same order: head, tail, edge id) and the
-// out-CSR (tail, head, edge id) without self-loops, parallel arcs kept
-int ensure_ties(shd_route* c) {
-    if (c->ti_ready) return SHD_ROUTE_OK;
-    int rc = ensure_hops(c);
-    if (rc) return rc;
-    const int n = c->n;
-    std::vector<int> head, tail, eid;
-    for (int e = 0; e < c->m; e++) {
-        const int a = c->e_src[e], b = c->e_dst[e];
-        if (a == b) continue;
-        head.push_back(b); tail.push_back(a); eid.push_back(e);
-        if (!c->directed) { head.push_back(a); tail.push_back(b); eid.push_back(e); }
-    }
-    const size_t k = head.size();
-    std::vector<size_t> idx(k);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-        if (head[x] != head[y]) return head[x] < head[y];
-        if (tail[x] != tail[y]) return tail[x] < tail[y];
-        return eid[x] < eid[y];
-    });
-    std::vector<double> r(k);
-    for (size_t q = 0; q < k; q++) r[q] = c->e_rel[eid[idx[q]]];
-    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-        if (tail[x] != tail[y]) return tail[x] < tail[y];
-        if (head[x] != head[y]) return head[x] < head[y];
-        return eid[x] < eid[y];
-    });
-    std::vector<int> row(n + 1, 0), hd(k);
-    std::vector<double> w(k);
-    for (size_t q = 0; q < k; q++) {
-        const size_t a = idx[q];
-        row[tail[a] + 1]++;
-        hd[q] = head[a];
-        w[q] = c->e_lat[eid[a]];
-    }
-    for (int v = 0; v < n; v++) row[v + 1] += row[v];
-    rc = upload(c, &c->d_ti_r, r);
-    if (!rc) rc = upload(c, &c->d_ti_row, row);
-    if (!rc) rc = upload(c, &c->d_ti_head, hd);
-    if (!rc) rc = upload(c, &c->d_ti_w, w);
-    if (!rc && ties_fits_lds(n))
-        rc = hip_check(hipFuncSetAttribute((const void*)ties_dag_kernel<uint16_t, true, 1024>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(kTiSmall + TiesLayout<uint16_t>::make(n).total)));
-    if (rc) return rc;
-    c->ti_ready = 1;
-    return SHD_ROUTE_OK;
-}
-
-DevTies dev_ties(const shd_route* c) {
-    DevTies q;
-    q.r_in = c->d_ti_r; q.row_out = c->d_ti_row; q.head_out = c->d_ti_head; q.w_out = c->d_ti_w;
-    q.vf = c->d_vf; q.self_r = c->d_self_r;
-    return q;
-}
-
-// dist (k x n f64) = the all-vertex latency rows of the sources, rem (k x n u32) the tight
-// in-degree of every vertex under each
-int ti_rows(shd_route* c, const int32_t* d_src, int k, double* dist, uint32_t* rem, hipStream_t st) {
-    const int n = c->n;
-    hipLaunchKernelGGL(hops_err_park_kernel, dim3(1), dim3(1), 0, st, c->d_err, c->d_hp_saved);
-    int rc = shd_route_rows_async(c, d_src, k, c->d_hp_ident, n, n, 0u, dist, nullptr, nullptr, st);
-    hipLaunchKernelGGL(hops_err_unpark_kernel, dim3(1), dim3(1), 0, st, c->d_err, (const int*)c->d_hp_saved);
-    if (rc) return rc;
-    const dim3 grid((unsigned)std::min((n + 255) / 256, 4096), (unsigned)std::min(k, 65535));
-    hipLaunchKernelGGL(ties_indeg_kernel<256>, grid, dim3(256), 0, st, dev_hops(c), (const double*)dist, (long long)n,
-                       d_src, k, rem, (long long)n);
-    return hip_check(hipGetLastError());
-}
-
-// the sweep of k sources and their entries (ties_dag_kernel), state in LDS or in HBM slices
-int ti_dag(shd_route* c, const double* dist, const uint32_t* rem, const int32_t* d_src, int k, const int32_t* d_tgt,
-           int nt, long long ld, int mode, uint64_t* d_count, double* d_lo, double* d_hi, hipStream_t st) {
-    const int n = c->n;
-    const DevHops g = dev_hops(c);
-    const DevTies q = dev_ties(c);
-    auto* cnt = (unsigned long long*)d_count;
-    if (mode == 2) {  // no rows, no DAG, no state
-        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, false, 1024>), dim3(std::min(k, 1024)), dim3(1024), kTiSmall, st,
-                           g, q, dist, rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, (char*)nullptr, (size_t)0,
-                           c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    const bool small = n <= 65535;
-    const size_t lds_bytes = kTiSmall + TiesLayout<uint16_t>::make(n).total;
-    const char* e = getenv("SHD_ROUTE_TIES_LDS");  // "0": the HBM form on graphs the LDS form takes
-    if (ties_fits_lds(n) && !(e && *e && atoi(e) == 0)) {
-        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, true, 1024>), dim3(std::min(k, 1024)), dim3(1024), lds_bytes, st,
-                           g, q, dist, rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, (char*)nullptr, (size_t)0,
-                           c->d_err);
-        return hip_check(hipGetLastError());
-    }
-    // HBM slices: a quarter of the hops scratch budget, 16 to 512 workgroup slots (as the loads)
-    const size_t stride = a16(small ? TiesLayout<uint16_t>::make(n).total : TiesLayout<uint32_t>::make(n).total);
-    const int slots = (int)std::max<size_t>(16, std::min<size_t>(512, hp_budget() / 4 / stride));
-    const int grid = std::min(k, slots);
-    if (stride * (size_t)grid > c->ti_ws_cap) {
-        // a launch of this context that still uses the old slices is on the same stream or
-        // synchronised (one rows launch at a time): wait before the slices go
-        if (c->d_ti_ws) {
-            if (hipStreamSynchronize(st) != hipSuccess) return SHD_ROUTE_EDEVICE;
-            (void)hipFree(c->d_ti_ws);
-        }
-        c->d_ti_ws = nullptr;
-        c->ti_ws_cap = 0;
-        if (hipMalloc((void**)&c->d_ti_ws, stride * (size_t)slots) != hipSuccess) return SHD_ROUTE_ENOMEM;
-        c->ti_ws_cap = stride * (size_t)slots;
-    }
-    if (small)
-        hipLaunchKernelGGL((ties_dag_kernel<uint16_t, false, 1024>), dim3(grid), dim3(1024), kTiSmall, st, g, q, dist,
-                           rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, c->d_ti_ws, stride, c->d_err);
-    else
-        hipLaunchKernelGGL((ties_dag_kernel<uint32_t, false, 1024>), dim3(grid), dim3(1024), kTiSmall, st, g, q, dist,
-                           rem, d_src, k, d_tgt, nt, ld, mode, cnt, d_lo, d_hi, c->d_ti_ws, stride, c->d_err);
-    return hip_check(hipGetLastError());
-}
-
-}  // namespace
-
-extern "C" {
-
-int shd_route_ties_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
-                         int64_t ld, uint32_t flags, uint64_t* d_count, double* d_rel_lo, double* d_rel_hi,
-                         void* stream) {
-    if (!c || ns < 0 || nt < 0 || (ns && !d_src) || (nt && !d_tgt) || ld < nt) return SHD_ROUTE_EINVAL;
-    if (ns == 0) return SHD_ROUTE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    int rc = ensure_ties(c);
-    if (rc) return rc;
-    const int mode = hp_mode(c, flags);
-    if (mode == 2)
-        return ti_dag(c, nullptr, nullptr, d_src, ns, d_tgt, nt, (long long)ld, 2, d_count, d_rel_lo, d_rel_hi, st);
-    const size_t per = (size_t)c->n * (sizeof(double) + sizeof(uint32_t));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)ns, hp_budget() / per));
-    if ((rc = hp_scratch(c, per * (size_t)chunk))) return rc;
-    double* dist = (double*)c->d_hp_buf;
-    uint32_t* rem = (uint32_t*)(c->d_hp_buf + sizeof(double) * (size_t)c->n * (size_t)chunk);
-    for (int i0 = 0; i0 < ns; i0 += chunk) {
-        const int k = std::min(chunk, ns - i0);
-        if ((rc = ti_rows(c, d_src + i0, k, dist, rem, st))) return rc;
-        if ((rc = ti_dag(c, dist, rem, d_src + i0, k, d_tgt, nt, (long long)ld, mode,
-                         d_count ? d_count + (long long)i0 * ld : nullptr,
-                         d_rel_lo ? d_rel_lo + (long long)i0 * ld : nullptr,
-                         d_rel_hi ? d_rel_hi + (long long)i0 * ld : nullptr, st)))
-            return rc;
-    }
-    return SHD_ROUTE_OK;
-}
-
-int shd_route_ties(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
-                   uint64_t* count_out, double* rel_lo_out, double* rel_hi_out) {
-    if (!c || ns < 0 || nt < 0 || (ns && !src) || (nt && !tgt)) return SHD_ROUTE_EINVAL;
-    if (ns == 0) return SHD_ROUTE_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
-    // rows of the three outputs per device chunk: up to 1 GiB
-    const size_t row_elems = (size_t)std::max(nt, 1);
-    const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(ns, (size_t)(1u << 30) / (24 * row_elems)));
-    DevBuf dsrc, dtgt, dc, dl, dh;
-    int rc;
-    if ((rc = dsrc.alloc(sizeof(int32_t) * ns)) || (rc = dtgt.alloc(sizeof(int32_t) * std::max(nt, 1))) ||
-        (count_out && (rc = dc.alloc(sizeof(uint64_t) * row_elems * chunk))) ||
-        (rel_lo_out && (rc = dl.alloc(sizeof(double) * row_elems * chunk))) ||
-        (rel_hi_out && (rc = dh.alloc(sizeof(double) * row_elems * chunk))))
-        return rc;
-    if (hipMemcpy(dsrc.p, src, sizeof(int32_t) * ns, hipMemcpyHostToDevice) != hipSuccess ||
-        (nt && hipMemcpy(dtgt.p, tgt, sizeof(int32_t) * nt, hipMemcpyHostToDevice) != hipSuccess))
-        return SHD_ROUTE_EDEVICE;
-    int soft = SHD_ROUTE_OK;
-    for (int32_t i0 = 0; i0 < ns; i0 += chunk) {
-        const int32_t k = std::min(chunk, ns - i0);
-        rc = shd_route_ties_async(c, (const int32_t*)dsrc.p + i0, k, (const int32_t*)dtgt.p, nt, nt, flags,
-                                  count_out ? (uint64_t*)dc.p : nullptr, rel_lo_out ? (double*)dl.p : nullptr,
-                                  rel_hi_out ? (double*)dh.p : nullptr, nullptr);
-        if (rc) return rc;
-        if ((rc = shd_route_sync(c, nullptr)) && rc != SHD_ROUTE_ENOEDGE && rc != SHD_ROUTE_EUNREACH) return rc;
-        if (rc && !soft) soft = rc;
-        const size_t cnt = (size_t)nt * k;
-        if (nt && ((count_out && hipMemcpy(count_out + (size_t)i0 * nt, dc.p, sizeof(uint64_t) * cnt,
-                                           hipMemcpyDeviceToHost) != hipSuccess) ||
-                   (rel_lo_out && hipMemcpy(rel_lo_out + (size_t)i0 * nt, dl.p, sizeof(double) * cnt,
-                                            hipMemcpyDeviceToHost) != hipSuccess) ||
-                   (rel_hi_out && hipMemcpy(rel_hi_out + (size_t)i0 * nt, dh.p, sizeof(double) * cnt,
-                                            hipMemcpyDeviceToHost) != hipSuccess)))
-            return SHD_ROUTE_EDEVICE;
-    }
     return soft;
 }
 

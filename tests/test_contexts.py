@@ -1,6 +1,7 @@
 """Several live contexts (CPU part): the pairs of graphs tests/test_contexts_gpu.py keeps alive
 together, one pair per kernel function whose dynamic-LDS limit a context sets for itself
-(hipFuncSetAttribute in engine.hip apply_selection, shd_route_create, fw_prepare, ensure_hops).
+(hipFuncSetAttribute in engine.hip apply_selection, shd_route_create, fw_prepare; path_calls.hpp
+ensure_hops).
 The limit belongs to the function, not to the context, so the second context of a pair moves
 it under the first one's feet.  For that to be tried, the two must ask for different amounts:
 here, without a GPU, every pair is held to

@@ -7,7 +7,7 @@ for the launches below the other suites never pass more sources than the cap, so
 workgroup runs one source.  Sources may repeat in every entry point, so each cap is crossed on
 a graph of a few hundred vertices:
 
-  launch (engine.hip)                                   cap             sources here
+  launch (engine.hip; the path calls: path_calls.hpp)   cap             sources here
   fw_rows_kernel                                        2048            2048 + 7
   fw_parent_kernel (SHD_ROUTE_FWP8=0)                   8192            8192 + 7
   fw_parent8_kernel                                     2048 x 8        16384 + 9 (ragged last group)
@@ -47,7 +47,7 @@ pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-# the caps, as engine.hip states them
+# the caps, as engine.hip and path_host.hpp (state_form) state them
 FW_ROWS_CAP = 2048
 FW_PARENT_CAP = 8192
 FW_PARENT8_CAP = 2048 * 8
@@ -239,7 +239,7 @@ def loads_ref(name, idx, W):
 
 
 def slots_of(stride):
-    """engine.hip: the HBM slices take a quarter of the 1 GiB scratch budget, 16 to 512 slots."""
+    """path_host.hpp state_form: the HBM slices take a quarter of the 1 GiB scratch budget, 16 to 512 slots."""
     return max(16, min(TREE_HBM_SLOTS, ((1 << 30) // 4) // stride))
 
 

@@ -81,6 +81,12 @@ def _graph(name):
     if name == "ba60_multi":
         g = _multi()
         return g, np.arange(g.n, dtype=np.int32)
+    if name == "ba60_holes":
+        # ba60 (a self-loop at every vertex) without the self-loops of the odd vertices
+        g, A = _graph("ba60")
+        keep = ~((g.src == g.dst) & (g.src % 2 == 1))
+        return Graph(n=g.n, src=g.src[keep], dst=g.dst[keep], latency=g.latency[keep], packetloss=g.packetloss[keep],
+                     vertex_packetloss=g.vertex_packetloss, name=name), A
     z = np.load(os.path.join(GOLD, "small_tables.npz"))
     p = f"{name}__"
     vl = z[p + "vertex_packetloss"]
@@ -362,6 +368,48 @@ def test_fallbacks(route, monkeypatch, name, var):
     assert base[0].max() == (514 if name == "ring515" else _oracle_hops(name, 16).max())
     for a, b in zip(base, got):
         assert np.array_equal(a, b)
+
+
+def test_paths_in_chunks_with_failed_pairs(route, monkeypatch):
+    """ba60_holes, 16 sources, scratch for four sources per chunk: shd_route_paths takes the
+    sorted sources in four chunks.  The self pairs of the odd sources of the two middle chunks
+    fail (no self-loop) and take no room, so every path behind them is staged and copied out
+    at an offset that the chunks before it moved.  Offsets, vertices, edges and the code equal
+    the run in one chunk."""
+    g, _ = _graph("ba60_holes")
+    A = np.arange(2, 50, 3, dtype=np.int32)              # sorted: chunks of A[0:4] .. A[12:16]
+    rng = np.random.default_rng(16)
+    S, T = _all_pairs(A, g.n, rng, dup=10)
+    keep = S != T
+    holes = A[4:12][A[4:12] % 2 == 1]                    # in neither the first nor the last chunk
+    loops = A[A % 2 == 0]
+    assert len(holes) == 4 and all(_self_eid(g, int(v)) < 0 for v in holes)
+    assert all(_self_eid(g, int(v)) >= 0 for v in loops)
+    S = np.concatenate([S[keep], holes, loops]); T = np.concatenate([T[keep], holes, loops])
+    k = rng.permutation(len(S))
+    S, T = S[k], T[k]
+
+    def paths():
+        with pytest.raises(route.RouteError) as err:
+            route.RouteEngine(g).paths(S, T, dispatch=False)
+        return err.value.code, err.value.partial
+
+    code0, base = paths()
+    monkeypatch.setenv("SHD_ROUTE_HOPS_SCRATCH", str(4 * 16 * g.n))
+    code1, got = paths()
+    assert code0 == code1 == route.ENOEDGE
+    for a, b in zip(base, got):
+        assert np.array_equal(a, b)
+    off, vert, edge = got
+    failed = np.isin(S, holes) & (S == T)
+    assert np.array_equal(np.diff(off) == 0, failed)
+    sp = split_paths(route, off, vert, edge)
+    for q in np.flatnonzero(~failed):
+        assert sp[q][0][0] == S[q] and sp[q][0][-1] == T[q]
+    ok = ~failed & (S != T)
+    o2 = np.concatenate([[0], np.cumsum(np.diff(off)[ok])])
+    v2 = np.concatenate([sp[q][0] for q in np.flatnonzero(ok)]); e2 = np.concatenate([sp[q][1] for q in np.flatnonzero(ok)])
+    check_chain("ba60_holes", route, S[ok], T[ok], o2, v2, e2)
 
 
 def test_kernel_kf_same_paths(route, monkeypatch):

@@ -364,6 +364,36 @@ def test_sparse_equals_dense(route, name, dispatch):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("weighted", [True, False])
+def test_pair_loads_in_chunks(route, monkeypatch, weighted):
+    """ba60, the shuffled and split pairs of test_sparse_equals_dense over 12 sources, with scratch
+    for three sources per chunk: the sparse lists run in four chunks, whose offsets index the one
+    target list and the one weight list of the whole call.  Edge loads, transit, unrouted and the
+    code equal the run in one chunk and the dense loads of the same block."""
+    g, A = _graph("ba60")
+    S = A[:12]; T = np.arange(g.n, dtype=np.int32)
+    assert len(np.unique(S)) == 12
+    rng = np.random.default_rng(12)
+    W = weights(rng, S, T)
+    ps = np.repeat(S, g.n); pt = np.tile(T, len(S)); pw = W.reshape(-1).copy()
+    dup = rng.choice(len(ps), size=100, replace=False)
+    half = pw[dup] // np.uint64(2)
+    pw[dup] -= half
+    ps = np.concatenate([ps, ps[dup]]); pt = np.concatenate([pt, pt[dup]]); pw = np.concatenate([pw, half])
+    k = rng.permutation(len(ps))
+    if not weighted:                        # unit weights: how many of the listed pairs route over each link
+        W = np.ones((len(S), g.n), np.uint64)
+        np.add.at(W.reshape(-1), dup, np.uint64(1))
+    pw = pw[k] if weighted else None
+    dense = run(route, route.RouteEngine(g).loads, S, T, W, dispatch=False)
+    whole = run(route, route.RouteEngine(g).pair_loads, ps[k], pt[k], pw, dispatch=False)
+    monkeypatch.setenv("SHD_ROUTE_HOPS_SCRATCH", str(3 * 16 * g.n))
+    got = run(route, route.RouteEngine(g).pair_loads, ps[k], pt[k], pw, dispatch=False)
+    assert got[0].any() and got[1].any()
+    for a, b, c in zip(got, whole, dense):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+
+
 def test_add_flag(route):
     g, A = _graph("ba60")
     eng = route.RouteEngine(g)
