@@ -13,7 +13,8 @@
  * on one stream, or synchronise in between).  The path hops calls (shd_route_hops*,
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
  * rows launch inside and fall under the same rule, and so do the tie envelope calls
- * (shd_route_ties*).
+ * (shd_route_ties*) and the ECMP link loads calls (shd_route_ecmp_loads*,
+ * shd_route_pair_ecmp_loads).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -35,14 +36,15 @@
  * device.  The calls that may block the host, and when:
  *   first use      shd_route_rows_async with SHD_ROUTE_DISPATCH on a complete graph,
  *                  shd_route_fw_table_async (the dense tables, built on the host and copied);
- *                  the hops, loads and ties calls (their in-CSR with edge ids; the ties calls
- *                  also their per-arc reliabilities and out-CSR); all once per context
+ *                  the hops, loads, ties and ECMP loads calls (their in-CSR with edge ids; the
+ *                  ties and ECMP loads calls also their per-arc reliabilities and out-CSR, the
+ *                  ECMP loads calls the out-arcs' edge ids); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
- *                  the hops, loads and ties calls when their source chunk grows,
- *                  shd_route_loads_async and shd_route_ties_async in their HBM forms when the
- *                  slices grow (those synchronise the stream)
+ *                  the hops, loads, ties and ECMP loads calls when their source chunk grows,
+ *                  shd_route_loads_async, shd_route_ties_async and shd_route_ecmp_loads_async in
+ *                  their HBM forms when the slices grow (those synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -72,6 +74,8 @@
  *                         per-router traffic of the chosen paths)
  *   shd_route_ties     <- (no reference equivalent; how many shortest paths tie and how far
  *                         any tie rule, igraph's heap order included, can move reliability)
+ *   shd_route_ecmp_loads, shd_route_pair_ecmp_loads <- (no reference equivalent; per-link and
+ *                         per-router traffic split evenly over all tied shortest paths)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -313,6 +317,72 @@ int shd_route_ties_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, con
 /* Same with host pointers (row stride nt); blocks. */
 int shd_route_ties(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
                    uint32_t flags, uint64_t* count_out, double* rel_lo_out, double* rel_hi_out);
+
+/* ---- ECMP link loads: every entry's weight split evenly over all of its shortest paths ----
+ * No reference equivalent.  shd_route_loads* put all of a pair's weight on the one path the tie
+ * rule picks; routers with equal-cost multipath spread it over the tied paths.  With weight 1
+ * on all pairs the outputs are the edge and vertex betweenness centrality (ordered pairs,
+ * endpoints excluded).  Entries are those of shd_route_hops*, same flags; a shortest path is
+ * what shd_route_ties defines: a chain of tight arcs, d[u] + w_e == d[v] in f64, over the
+ * all-vertex latency row of the source with d[s] taken as 0.0; self-loops are not arcs,
+ * parallel tight edges are distinct paths.  sigma_s(v) = the number of shortest paths s -> v as
+ * f64: exact below 2^53 and rounded above; it never saturates.
+ *   t != s : w is split evenly over the sigma_s(t) shortest paths: every edge id on a path
+ *            gets that path's w / sigma_s(t) in edge_load, every intermediate vertex of the path
+ *            gets it in transit; the endpoints s and t get none.  Summed per source this is the
+ *            programme own[x] = the sum of the weights of the entries with target x,
+ *            delta[v] = the sum over the tight out-arcs (v -> x, e) of f_e,
+ *            f_e = (sigma[v] / sigma[x]) * (own[x] + delta[x]); edge_load[e] += f_e, and
+ *            transit[v] += delta[v] for v != s (Brandes' dependency accumulation).
+ *   t == s : w goes on the lowest self-loop edge of s, no transit; without a self-loop the
+ *            entry fails with SHD_ROUTE_ENOEDGE.
+ *   unreachable t : the entry fails with SHD_ROUTE_EUNREACH.
+ * With SHD_ROUTE_DISPATCH a complete graph, or prefer-direct with an adjacent pair, puts the
+ * whole w on the direct edge (the lowest edge id joining the pair), no transit; on a complete
+ * graph no rows launch and no sweep run.  A failed entry never stops the rest; it fails
+ * whatever its weight, and its weight is added to *unrouted, which stays a uint64_t: an exact
+ * integer sum (modulo 2^64), as in the loads.  The code comes back at the end
+ * (shd_route_ecmp_loads, shd_route_pair_ecmp_loads) or by the next shd_route_sync
+ * (shd_route_ecmp_loads_async).  On an undirected graph an edge has one load for both
+ * directions.
+ *   Weights stay uint64_t (packet counts).  Repeated targets of one source and repeated pairs
+ * are summed as integers, modulo 2^64, and that sum is converted to f64 once.  The loads are
+ * doubles.  Every quantity of the programme is non-negative and nothing is subtracted
+ * (transit is delta, not "sum minus own"), so errors stay relative: an element whose exact
+ * value is 0 is exactly 0.  Where every listed pair has exactly one shortest path and the
+ * totals are below 2^53 the result equals shd_route_loads converted to double, exactly.
+ *   Reproducibility: the programme of one source has a fixed order (tight arcs in the order of
+ * the in- and out-CSR: by neighbour, then edge id; lists of more than 32 arcs are summed by a
+ * wave in a fixed tree) and is reproducible to the bit.  The sums across sources into the
+ * outputs are floating-point atomic adds in the order they arrive: a call with more than two
+ * sources is reproducible to rounding, not to the bit.  With R the deepest level of any source
+ * of the call, D the largest number of tight in- or out-arcs of a vertex and A = ns * (1 + the
+ * largest multiplicity of one pair), every element is within
+ * ((R+1)*(2*(R+1)*D + D + 4) + A) * 2^-52 relative of the exact value.
+ *   The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the ties calls' scratch: per source of a chunk an f64 distance row and a u32 row (the
+ * tight in-degrees), chunks sized to SHD_ROUTE_HOPS_SCRATCH (1 GiB).  One workgroup per source
+ * sweeps the DAG of tight arcs forwards, level by level, for sigma, and backwards for delta;
+ * its state (34 bytes per vertex while n <= 65535, 36 above) lives in LDS or, on larger graphs
+ * and with SHD_ROUTE_ECMP_LDS=0, in HBM slices of 16 to 512 workgroup slots within a quarter of
+ * that budget.  Diagnostic rate: every call runs the sources' SSSP.  SHD_ROUTE_LOADS_ADD adds
+ * into the outputs instead of zeroing them first. */
+/* Device pointers, as shd_route_loads_async: d_wt[i*ld + j] = the weight of (src[i], tgt[j]),
+ * NULL = 1 per entry; d_edge_load[n_edges], d_transit[n_vertices] (memory of hipMalloc),
+ * d_unrouted[1]; any output may be NULL. */
+int shd_route_ecmp_loads_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                               int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                               double* d_edge_load, double* d_transit, uint64_t* d_unrouted, void* stream);
+/* Same with host pointers (row stride nt); blocks.  A vertex out of range is SHD_ROUTE_EINVAL
+ * for the whole call, nothing written. */
+int shd_route_ecmp_loads(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                         uint32_t flags, const uint64_t* wt, double* edge_load_out, double* transit_out,
+                         uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[k], pair_tgt[k], pair_wt[k]) in any order (pair_wt NULL =
+ * 1 each), grouped by source inside as shd_route_paths groups them.  Host pointers; blocks. */
+int shd_route_pair_ecmp_loads(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                              const uint64_t* pair_wt, int64_t npairs, uint32_t flags, double* edge_load_out,
+                              double* transit_out, uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

@@ -168,6 +168,12 @@ int64_t shd_topology_route_line(char** buf, size_t* cap, char* const* names, con
  * first fill every total is zero. */
 int shd_topology_link_loads(shd_topology_t* top, uint64_t* edge_packets, uint64_t* transit_packets,
                             uint64_t* unrouted);
+/* The same pairs, counters and dispatch with every pair's packets split evenly over all of its
+ * shortest paths (shd_route_pair_ecmp_loads: what equal-cost multipath routers would carry), in
+ * double; *unrouted stays an exact integer.  Same rules: engine 0, nothing cached, every total
+ * zero before the first fill; each output may be NULL. */
+int shd_topology_ecmp_link_loads(shd_topology_t* top, double* edge_packets, double* transit_packets,
+                                 uint64_t* unrouted);
 /* One line per edge with a non-zero total, in edge-id order:
  *   link A<-->B (i<-->j) edge E is L ms with P loss, N packets
  * ("-->" on directed graphs; A, B = the edge's ends as the graph lists them, named as in the

@@ -27,6 +27,7 @@
 #include "path_hops.hpp"
 #include "link_loads.hpp"
 #include "path_ties.hpp"
+#include "ecmp_loads.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 #include "path_host.hpp"

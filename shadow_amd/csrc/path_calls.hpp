@@ -1,9 +1,10 @@
 #pragma once
 // path_calls.hpp -- the path calls of the engine: hop counts and explicit routes
-// (path_hops.hpp), link loads (link_loads.hpp) and the tie envelope (path_ties.hpp), over one
-// set of host stages.  What needs no device is path_host.hpp; here are the uploads, the
-// launches and the entry points.  Not a stand-alone header: engine.hip includes it once
-// struct shd_route, hip_check, upload, DevBuf and shd_route_rows_async are defined.
+// (path_hops.hpp), link loads (link_loads.hpp), the tie envelope (path_ties.hpp) and the ECMP
+// link loads (ecmp_loads.hpp), over one set of host stages.  What needs no device is
+// path_host.hpp; here are the uploads, the launches and the entry points.  Not a stand-alone
+// header: engine.hip includes it once struct shd_route, hip_check, upload, DevBuf and
+// shd_route_rows_async are defined.
 
 namespace {
 
@@ -117,6 +118,25 @@ int ensure_ties(shd_route* c) {
     return SHD_ROUTE_OK;
 }
 
+// and for the ECMP loads the edge id of every arc of that out-CSR, in its order
+int ensure_ecmp(shd_route* c) {
+    PathDev& p = c->path;
+    if (p.ec_ready) return SHD_ROUTE_OK;
+    int rc = ensure_ties(c);
+    if (rc) return rc;
+    const int n = c->n;
+    const PathArcs arcs(n, c->directed, c->e_src, c->e_dst);
+    const PathCsr out = path_out_csr(n, arcs, c->e_lat.data(), c->e_rel);
+    rc = upload(c, &p.ec_eid, out.eid);
+    if (!rc && ecmp_fits_lds(n))
+        rc = hip_check(hipFuncSetAttribute((const void*)ecmp_dag_kernel<uint16_t, true, 1024>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(kEcSmall + EcmpLayout<uint16_t>::make(n).total)));
+    if (rc) return rc;
+    p.ec_ready = 1;
+    return SHD_ROUTE_OK;
+}
+
 DevHops dev_hops(const shd_route* c) {
     const PathDev& p = c->path;
     DevHops g;
@@ -135,7 +155,7 @@ DevTies dev_ties(const shd_route* c) {
 
 // the buffers grown on demand (shd_route_destroy; the uploads are in the context's allocs)
 void path_free(PathDev& p) {
-    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.buf})
+    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.buf})
         if (q) (void)hipFree(q);
 }
 
@@ -650,6 +670,187 @@ int shd_route_ties(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t
                 return r;
             return to_host(rel_hi_out ? rel_hi_out + o : nullptr, dh.p, bytes);
         });
+}
+
+}  // extern "C"
+
+// ---- ECMP link loads ----
+namespace {
+
+// the sweeps of k sources and their entries (ecmp_dag_kernel); HBM slices as the loads'
+int ec_dag(shd_route* c, const double* dist, const uint32_t* rem, const int32_t* d_src, int k, const int32_t* d_tgt,
+           int nt, long long ld, const long long* d_eoff, const uint64_t* d_wt, int mode, double* d_edge,
+           double* d_transit, uint64_t* d_unrouted, hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    const DevTies q = dev_ties(c);
+    const char* e = getenv("SHD_ROUTE_ECMP_LDS");  // "0": the HBM form on graphs the LDS form takes
+    const StateLaunch f = state_form(n, mode, k, kEcSmall, EcmpLayout<uint16_t>::make(n).total, kEcmpLdsBudget,
+                                     knob_off(e), a16(EcmpLayout<uint16_t>::make(n).total),
+                                     a16(EcmpLayout<uint32_t>::make(n).total), hp_budget() / 4);
+    return launch_state(c->path.ec_ws, f, st, [&](auto tag, char* ws, size_t stride) {
+        using F = decltype(tag);
+        hipLaunchKernelGGL((ecmp_dag_kernel<typename F::t, F::lds, 1024>), dim3(f.grid), dim3(1024), f.lds, st, g, q,
+                           (const int*)c->path.ec_eid, dist, rem, d_src, k, d_tgt, nt, ld, d_eoff,
+                           (const unsigned long long*)d_wt, mode, d_edge, d_transit, (unsigned long long*)d_unrouted,
+                           ws, stride, c->d_err);
+    });
+}
+
+// The ECMP loads of ns sources added into the outputs; entries as ld_sources takes them.  Per
+// chunk, as shd_route_ties_async: the sources' all-vertex latency rows, the tight in-degree of
+// every vertex under each, then the sweeps.
+int ec_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
+               const long long* d_eoff, const uint64_t* d_wt, uint32_t flags, double* d_edge, double* d_transit,
+               uint64_t* d_unrouted, hipStream_t st) {
+    int rc = ensure_ecmp(c);
+    if (rc) return rc;
+    const int mode = hp_mode(c, flags);
+    const int n = c->n;
+    return source_chunks(c, ns, mode, false, [&](int i0, int k, double* dist, uint32_t* rem, int32_t*) {
+        if (rem) {
+            if ((rc = all_vertex_rows(c, d_src + i0, k, dist, st))) return rc;
+            hipLaunchKernelGGL(ties_indeg_kernel<256>, per_vertex_grid(c, k), dim3(256), 0, st, dev_hops(c),
+                               (const double*)dist, (long long)n, d_src + i0, k, rem, (long long)n);
+            if ((rc = hip_check(hipGetLastError()))) return rc;
+        }
+        return ec_dag(c, dist, rem, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr,
+                      d_wt && !d_eoff ? d_wt + (long long)i0 * ld : d_wt, mode, d_edge, d_transit, d_unrouted, st);
+    });
+}
+
+// zero the outputs a call without SHD_ROUTE_LOADS_ADD starts from (0.0 is all bits zero)
+int ec_zero(shd_route* c, uint32_t flags, double* d_edge, double* d_transit, uint64_t* d_unrouted, hipStream_t st) {
+    return ld_zero(c, flags, reinterpret_cast<uint64_t*>(d_edge), reinterpret_cast<uint64_t*>(d_transit), d_unrouted,
+                   st);
+}
+
+// device accumulators of the blocking calls, as LoadsOut: the loads in double, unrouted in u64
+struct EcmpOut {
+    DevBuf de, dt, du;
+    int m = 0, n = 0;
+    int init(const shd_route* c) {
+        m = c->m; n = c->n;
+        int rc;
+        if ((rc = de.alloc(sizeof(double) * (size_t)m)) || (rc = dt.alloc(sizeof(double) * (size_t)n)) ||
+            (rc = du.alloc(sizeof(uint64_t))))
+            return rc;
+        if ((m && hipMemset(de.p, 0, sizeof(double) * (size_t)m) != hipSuccess) ||
+            hipMemset(dt.p, 0, sizeof(double) * (size_t)n) != hipSuccess ||
+            hipMemset(du.p, 0, sizeof(uint64_t)) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        return SHD_ROUTE_OK;
+    }
+    template <typename U>
+    static int take(U* out, const void* dev, size_t count, bool add) {
+        if (!add) return to_host(out, dev, sizeof(U) * count);
+        if (!out || !count) return SHD_ROUTE_OK;
+        std::vector<U> h(count);
+        if (int rc = to_host(h.data(), dev, sizeof(U) * count)) return rc;
+        for (size_t q = 0; q < count; q++) out[q] += h[q];
+        return SHD_ROUTE_OK;
+    }
+    int finish(uint32_t flags, double* edge_out, double* transit_out, uint64_t* unrouted_out) {
+        const bool add = (flags & SHD_ROUTE_LOADS_ADD) != 0;
+        int rc;
+        if ((rc = take(edge_out, de.p, (size_t)m, add)) || (rc = take(transit_out, dt.p, (size_t)n, add))) return rc;
+        return take(unrouted_out, du.p, 1, add);
+    }
+    // ns sources on the null stream into the accumulators
+    int add_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, const long long* d_eoff,
+                    const void* d_wt, uint32_t flags) {
+        return ec_sources(c, d_src, ns, d_tgt, nt, nt, d_eoff, (const uint64_t*)d_wt, flags, (double*)de.p,
+                          (double*)dt.p, (uint64_t*)du.p, nullptr);
+    }
+};
+
+// the outputs of a blocking call that has nothing to route
+void ec_host_zero(const shd_route* c, uint32_t flags, double* edge_out, double* transit_out, uint64_t* unrouted_out) {
+    if (flags & SHD_ROUTE_LOADS_ADD) return;
+    if (edge_out) std::fill(edge_out, edge_out + c->m, 0.0);
+    if (transit_out) std::fill(transit_out, transit_out + c->n, 0.0);
+    if (unrouted_out) *unrouted_out = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_ecmp_loads_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                               int64_t ld, uint32_t flags, const uint64_t* d_wt, double* d_edge_load, double* d_transit,
+                               uint64_t* d_unrouted, void* stream) {
+    if (!block_args_ok(c, d_src, ns, d_tgt, nt, ld)) return SHD_ROUTE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    int rc = ec_zero(c, flags, d_edge_load, d_transit, d_unrouted, st);
+    if (rc || ns == 0 || nt == 0) return rc;
+    return ec_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, d_wt, flags, d_edge_load, d_transit, d_unrouted,
+                      st);
+}
+
+int shd_route_ecmp_loads(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                         uint32_t flags, const uint64_t* wt, double* edge_load_out, double* transit_out,
+                         uint64_t* unrouted_out) {
+    if (!block_args_ok(c, src, ns, tgt, nt, nt)) return SHD_ROUTE_EINVAL;
+    for (int32_t i = 0; i < ns; i++)
+        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
+    for (int32_t j = 0; j < nt; j++)
+        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
+    if (ns == 0 || nt == 0) {
+        ec_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)nt;
+    const int32_t chunk = host_chunk(ns, row_bytes);
+    DevBuf dw;
+    EcmpOut out;
+    int rc;
+    if ((wt && (rc = dw.alloc(row_bytes * chunk))) || (rc = out.init(c))) return rc;
+    return host_blocks(
+        c, src, ns, tgt, nt, chunk,
+        [&](int32_t i0, int32_t k, const int32_t* d_src, const int32_t* d_tgt) {
+            if (wt && hipMemcpy(dw.p, wt + (size_t)i0 * nt, row_bytes * k, hipMemcpyHostToDevice) != hipSuccess)
+                return SHD_ROUTE_EDEVICE;
+            return out.add_sources(c, d_src, k, d_tgt, nt, nullptr, wt ? dw.p : nullptr, flags);
+        },
+        [&](int32_t i0, int32_t k) {
+            return i0 + k < ns ? SHD_ROUTE_OK : out.finish(flags, edge_load_out, transit_out, unrouted_out);
+        });
+}
+
+int shd_route_pair_ecmp_loads(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt,
+                              const uint64_t* pair_wt, int64_t npairs, uint32_t flags, double* edge_load_out,
+                              double* transit_out, uint64_t* unrouted_out) {
+    if (!pair_args_ok(c, pair_src, pair_tgt, npairs) || !pairs_in_range(c, pair_src, pair_tgt, (int)npairs))
+        return SHD_ROUTE_EINVAL;
+    const int np = (int)npairs;
+    if (np == 0) {
+        ec_host_zero(c, flags, edge_load_out, transit_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // the entries of distinct source u are the grouped positions first[u] .. first[u + 1]
+    const PairGroups pg = group_pairs(pair_src, pair_tgt, pair_wt, np);
+    const int nu = (int)pg.us.size();
+    DevBuf dsrc, dtgt, dw, doff;
+    EcmpOut out;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
+        (pair_wt && (rc = dw.alloc(sizeof(uint64_t) * (size_t)np))) ||
+        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) || (rc = out.init(c)))
+        return rc;
+    if (hipMemcpy(dsrc.p, pg.us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, pg.gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
+        (pair_wt && hipMemcpy(dw.p, pg.gw.data(), sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(doff.p, pg.first.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess)
+        return SHD_ROUTE_EDEVICE;
+    SoftCode sc;
+    if ((rc = out.add_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, (const long long*)doff.p,
+                              pair_wt ? dw.p : nullptr, flags)) ||
+        (rc = sc.sync(c)) || (rc = out.finish(flags, edge_load_out, transit_out, unrouted_out)))
+        return rc;
+    return sc.soft;
 }
 
 }  // extern "C"

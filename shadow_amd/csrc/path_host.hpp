@@ -1,5 +1,5 @@
 #pragma once
-// path_host.hpp -- what the path calls (hops, link loads, tie envelope: path_calls.hpp) decide
+// path_host.hpp -- what the path calls (hops, link loads, tie envelope, ECMP loads: path_calls.hpp) decide
 // without a device: the arcs they upload, the pairs of a call grouped by source, the source
 // chunks of the row scratch and the form each per-source state kernel launches in.  Host code
 // only (no hip* call): tests/path_host_main.cpp runs all of it on the CPU.
@@ -97,7 +97,8 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 }
 
 // ---- the form of a per-source state kernel ----
-// hops_depth_kernel, loads_tree_kernel and ties_dag_kernel keep one source's state per workgroup:
+// hops_depth_kernel, loads_tree_kernel, ties_dag_kernel and ecmp_dag_kernel keep one source's
+// state per workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
 // else u16 (n <= 65535) or u32 state in HBM slices, one per resident workgroup.
@@ -148,7 +149,10 @@ struct PathDev {
     int ti_ready = 0;
     double* ti_r = nullptr; int* ti_row = nullptr; int* ti_head = nullptr; double* ti_w = nullptr;
     int ld_ready = 0;  // loads: the LDS form's dynamic-LDS limit is raised
-    PathSlices hp_ws, ld_ws, ti_ws;
+    // ECMP loads: the edge id of every arc of the ties' out-CSR (built at the first ECMP call)
+    int ec_ready = 0;
+    int* ec_eid = nullptr;
+    PathSlices hp_ws, ld_ws, ti_ws, ec_ws;
     char* buf = nullptr;  // the row scratch (scratch_chunks), grown on demand
     size_t buf_cap = 0;
 };

@@ -742,12 +742,9 @@ int shd_topology_dump_routes(shd_topology_t* t, FILE* out) {
 /* ---- link loads: the cached Paths' packet counters summed per edge and per vertex
  * (shd_route_pair_loads on engine 0, nothing cached) ---- */
 
-int shd_topology_link_loads(shd_topology_t* t, uint64_t* edge_packets, uint64_t* transit_packets, uint64_t* unrouted) {
-    if (!t) return SHD_ROUTE_EINVAL;
-    if (edge_packets) memset(edge_packets, 0, sizeof(uint64_t) * (size_t)t->g.n_edges);
-    if (transit_packets) memset(transit_packets, 0, sizeof(uint64_t) * (size_t)t->n);
-    if (unrouted) *unrouted = 0;
-    pthread_mutex_lock(&t->lock);
+/* every cached pair with a non-zero packet count, in its stored orientation (lower attached
+ * vertex -> higher); the caller holds t->lock and frees the three lists */
+static int counted_pairs(shd_topology_t* t, int32_t** ps_out, int32_t** pt_out, uint64_t** pw_out, size_t* np_out) {
     /* the counters live in the current fill, or between a late attach and the next lookup in
      * the fill it retired; before the first fill there are none */
     pcache* c = t->cache ? t->cache : t->retired;
@@ -756,8 +753,8 @@ int shd_topology_link_loads(shd_topology_t* t, uint64_t* edge_packets, uint64_t*
     uint64_t* pw = NULL;
     size_t np = 0, pcap = 0;
     if (c) {
-        /* every pair with a non-zero count: the dense u32 counter plus its spill, the stripes
-         * locked once for the pass as carry_counters locks them */
+        /* the dense u32 counter plus its spill, the stripes locked once for the pass as
+         * carry_counters locks them */
         for (int k = 0; k < PC_STRIPES; k++) pthread_mutex_lock(&c->pc[k].lock);
         for (int32_t i = 0; i < c->na && !rc; i++)
             for (int32_t j = i; j < c->na; j++) {
@@ -780,17 +777,53 @@ int shd_topology_link_loads(shd_topology_t* t, uint64_t* edge_packets, uint64_t*
                     if (w2) pw = w2;
                     if (!s2 || !t2 || !w2) { rc = SHD_ROUTE_ENOMEM; break; }
                 }
-                ps[np] = c->A[i]; pt[np] = c->A[j]; pw[np] = v;  /* stored orientation: lower -> higher */
+                ps[np] = c->A[i]; pt[np] = c->A[j]; pw[np] = v;
                 np++;
             }
         for (int k = PC_STRIPES - 1; k >= 0; k--) pthread_mutex_unlock(&c->pc[k].lock);
     }
+    *ps_out = ps; *pt_out = pt; *pw_out = pw; *np_out = np;
+    return rc;
+}
+
+int shd_topology_link_loads(shd_topology_t* t, uint64_t* edge_packets, uint64_t* transit_packets, uint64_t* unrouted) {
+    if (!t) return SHD_ROUTE_EINVAL;
+    if (edge_packets) memset(edge_packets, 0, sizeof(uint64_t) * (size_t)t->g.n_edges);
+    if (transit_packets) memset(transit_packets, 0, sizeof(uint64_t) * (size_t)t->n);
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0;
+    int rc = counted_pairs(t, &ps, &pt, &pw, &np);
     if (!rc && np) {
         rc = shd_route_pair_loads(t->eng[0], ps, pt, pw, (int64_t)np, SHD_ROUTE_DISPATCH, edge_packets, transit_packets,
                                   unrouted);
         /* ENOEDGE: a self pair without a self-loop, stored as the path to self; its packets
          * are in *unrouted */
         if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;
+    }
+    pthread_mutex_unlock(&t->lock);
+    free(ps); free(pt); free(pw);
+    return rc;
+}
+
+/* the same pairs with every pair's packets split evenly over all of its shortest paths
+ * (shd_route_pair_ecmp_loads on engine 0, nothing cached) */
+int shd_topology_ecmp_link_loads(shd_topology_t* t, double* edge_packets, double* transit_packets, uint64_t* unrouted) {
+    if (!t) return SHD_ROUTE_EINVAL;
+    for (int32_t e = 0; edge_packets && e < t->g.n_edges; e++) edge_packets[e] = 0.0;
+    for (int32_t v = 0; transit_packets && v < t->n; v++) transit_packets[v] = 0.0;
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0;
+    int rc = counted_pairs(t, &ps, &pt, &pw, &np);
+    if (!rc && np) {
+        rc = shd_route_pair_ecmp_loads(t->eng[0], ps, pt, pw, (int64_t)np, SHD_ROUTE_DISPATCH, edge_packets,
+                                       transit_packets, unrouted);
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;  /* as above */
     }
     pthread_mutex_unlock(&t->lock);
     free(ps); free(pt); free(pw);

@@ -86,6 +86,7 @@ EXPORTS = (
     "shd_route_plan_bind_store", "shd_route_hops_async", "shd_route_hops", "shd_route_paths",
     "shd_route_plan_jobs", "shd_route_loads_async", "shd_route_loads", "shd_route_pair_loads",
     "shd_route_ties_async", "shd_route_ties",
+    "shd_route_ecmp_loads_async", "shd_route_ecmp_loads", "shd_route_pair_ecmp_loads",
 )
 
 _lib = None
@@ -174,6 +175,12 @@ def load_library():
     L.shd_route_ties_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P]
     L.shd_route_ties.restype = C.c_int
     L.shd_route_ties.argtypes = [P, P, I32, P, I32, U32, P, P, P]
+    L.shd_route_ecmp_loads_async.restype = C.c_int
+    L.shd_route_ecmp_loads_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P, P]
+    L.shd_route_ecmp_loads.restype = C.c_int
+    L.shd_route_ecmp_loads.argtypes = [P, P, I32, P, I32, U32, P, P, P, P]
+    L.shd_route_pair_ecmp_loads.restype = C.c_int
+    L.shd_route_pair_ecmp_loads.argtypes = [P, P, P, P, I64, U32, P, P, P]
     _lib = L
     return L
 
@@ -382,7 +389,67 @@ class RouteEngine:
         _check(rc, "shd_route_pair_loads")
         return el, tr, int(un[0])
 
+    def _ecmp_out(self, out):
+        if out is not None:
+            return out
+        return (np.zeros(self.info["n_edges"], np.float64), np.zeros(self.info["n_vertices"], np.float64),
+                np.zeros(1, np.uint64))
+
+    def ecmp_loads(self, sources, targets, weights=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_ecmp_loads: (edge_load, transit, unrouted) of the (source, target) block as
+        loads(), with every entry's weight split evenly over all of its shortest paths:
+        edge_load and transit are float64, unrouted stays an exact integer.  weights, out
+        (float64, float64 and a 1-element uint64 array) and add as loads().  A missing self-loop
+        or an unreachable target raises RouteError; ``err.partial`` then holds the results."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        el, tr, un = self._ecmp_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_ecmp_loads(self._h, _p(s), len(s), _p(t), len(t), flags, _p(w), _p(el), _p(tr),
+                                                 _p(un))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_ecmp_loads")
+            err.partial = (el, tr, int(un[0]))
+            raise err
+        _check(rc, "shd_route_ecmp_loads")
+        return el, tr, int(un[0])
+
+    def pair_ecmp_loads(self, pair_src, pair_tgt, pair_wt=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_pair_ecmp_loads: as ecmp_loads() for a list of (source, target, weight) pairs
+        in any order, repeats adding up (pair_wt None = 1 each)."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        el, tr, un = self._ecmp_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_pair_ecmp_loads(self._h, _p(s), _p(t), _p(w), len(s), flags, _p(el), _p(tr),
+                                                      _p(un))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_ecmp_loads")
+            err.partial = (el, tr, int(un[0]))
+            raise err
+        _check(rc, "shd_route_pair_ecmp_loads")
+        return el, tr, int(un[0])
+
     # -- device-pointer API (torch tensors as HBM plumbing) --------------------
+    def ecmp_loads_async(self, d_src, d_tgt, d_wt, d_edge_load, d_transit, d_unrouted, stream=None, dispatch=True,
+                         ld=None, add=False):
+        """shd_route_ecmp_loads_async over device tensors: int32 sources and targets, 64-bit
+        integer weights (None = 1 per entry), float64 edge loads and transit (n_edges,
+        n_vertices elements) and a 64-bit integer unrouted (1 element); any output may be None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_ecmp_loads_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0),
+            ptr(d_wt), ptr(d_edge_load), ptr(d_transit), ptr(d_unrouted), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_ecmp_loads_async")
+
     def loads_async(self, d_src, d_tgt, d_wt, d_edge_load, d_transit, d_unrouted, stream=None, dispatch=True,
                     ld=None, add=False):
         """shd_route_loads_async over device tensors: int32 sources and targets, 64-bit weights

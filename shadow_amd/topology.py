@@ -29,7 +29,7 @@ EXPORTS = (
     "shd_topology_fill", "shd_topology_dump_paths", "shd_topology_triangle_bytes",
     "shd_attach_create", "shd_attach_find_vertex", "shd_attach_destroy", "shd_topology_attach",
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
-    "shd_topology_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
+    "shd_topology_link_loads", "shd_topology_ecmp_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
@@ -113,6 +113,8 @@ def load_library():
     L.shd_topology_route_line.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), P, P, I32, P, P, D, D, C.c_int]
     L.shd_topology_link_loads.restype = C.c_int
     L.shd_topology_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_ecmp_link_loads.restype = C.c_int
+    L.shd_topology_ecmp_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_dump_link_loads.restype = C.c_int
     L.shd_topology_dump_link_loads.argtypes = [P, P]
     L.shd_topology_link_line.restype = C.c_int64
@@ -382,6 +384,20 @@ class Topology:
         rc = L.shd_topology_link_loads(self._h, C.c_void_p(ep.ctypes.data), C.c_void_p(tp.ctypes.data), C.byref(un))
         if rc:
             raise RuntimeError(f"link_loads failed ({rc})")
+        return ep, tp, int(un.value)
+
+    def ecmp_link_loads(self):
+        """shd_topology_ecmp_link_loads: (edge_packets, transit_packets, unrouted) as link_loads(),
+        every pair's packets split evenly over all of its shortest paths: float64 totals, an
+        exact integer unrouted."""
+        L = load_library()
+        ep = np.zeros(int(L.shd_topology_edge_count(self._h)), np.float64)
+        tp = np.zeros(int(L.shd_topology_vertex_count(self._h)), np.float64)
+        un = C.c_uint64()
+        rc = L.shd_topology_ecmp_link_loads(self._h, C.c_void_p(ep.ctypes.data), C.c_void_p(tp.ctypes.data),
+                                            C.byref(un))
+        if rc:
+            raise RuntimeError(f"ecmp_link_loads failed ({rc})")
         return ep, tp, int(un.value)
 
     def dump_link_loads(self, path: str):
