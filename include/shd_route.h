@@ -13,8 +13,8 @@
  * on one stream, or synchronise in between).  The path hops calls (shd_route_hops*,
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
  * rows launch inside and fall under the same rule, and so do the tie envelope calls
- * (shd_route_ties*) and the ECMP link loads calls (shd_route_ecmp_loads*,
- * shd_route_pair_ecmp_loads).
+ * (shd_route_ties*), the ECMP link loads calls (shd_route_ecmp_loads*,
+ * shd_route_pair_ecmp_loads) and the path fold calls (shd_route_fold*, shd_route_pair_fold).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -36,15 +36,16 @@
  * device.  The calls that may block the host, and when:
  *   first use      shd_route_rows_async with SHD_ROUTE_DISPATCH on a complete graph,
  *                  shd_route_fw_table_async (the dense tables, built on the host and copied);
- *                  the hops, loads, ties and ECMP loads calls (their in-CSR with edge ids; the
+ *                  the hops, loads, folds, ties and ECMP loads calls (their in-CSR with edge ids; the
  *                  ties and ECMP loads calls also their per-arc reliabilities and out-CSR, the
  *                  ECMP loads calls the out-arcs' edge ids); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
- *                  the hops, loads, ties and ECMP loads calls when their source chunk grows,
- *                  shd_route_loads_async, shd_route_ties_async and shd_route_ecmp_loads_async in
- *                  their HBM forms when the slices grow (those synchronise the stream)
+ *                  the hops, loads, folds, ties and ECMP loads calls when their source chunk
+ *                  grows, shd_route_loads_async, shd_route_fold_async, shd_route_ties_async and
+ *                  shd_route_ecmp_loads_async in their HBM forms when the slices grow (those
+ *                  synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -76,6 +77,9 @@
  *                         any tie rule, igraph's heap order included, can move reliability)
  *   shd_route_ecmp_loads, shd_route_pair_ecmp_loads <- (no reference equivalent; per-link and
  *                         per-router traffic split evenly over all tied shortest paths)
+ *   shd_route_fold, shd_route_pair_fold <- (no reference equivalent; any per-link quantity
+ *                         folded along the chosen paths, e.g. the jitter edge attribute the
+ *                         reference validates and drops, topology.c:1105-1114)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -383,6 +387,64 @@ int shd_route_ecmp_loads(shd_route_t* ctx, const int32_t* src, int32_t ns, const
 int shd_route_pair_ecmp_loads(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
                               const uint64_t* pair_wt, int64_t npairs, uint32_t flags, double* edge_load_out,
                               double* transit_out, uint64_t* unrouted_out);
+
+/* ---- path folds: sum, min, max and product of per-edge values along the chosen paths ------
+ * No reference equivalent: the reference folds latency and reliability only and drops the
+ * graphml's jitter after validating it (topology.c:1105-1114).  A call takes nf folds at once
+ * (1 <= nf <= SHD_ROUTE_FOLD_MAX_N) and pays for the sources' trees once: ops[k] is the op of
+ * fold k (a host array in all three calls, read at call time), val[k * n_edges + e] the value of
+ * edge id e for fold k (on an undirected graph an edge has one value for both directions), and
+ * out[k * plane + i * ld + j] fold k of the entry src[i] -> tgt[j].
+ *   Entries are those of shd_route_hops*, with the same flags:
+ *   t != s : the fold over the edge ids shd_route_paths reports for the entry, taken in order
+ *            from the source (on a multigraph each tree hop uses the lowest tight edge id of
+ *            that hop).
+ *   t == s : the fold over the lowest self-loop edge alone; without a self-loop the entry is NaN
+ *            and the code SHD_ROUTE_ENOEDGE.
+ *   unreachable t : NaN and SHD_ROUTE_EUNREACH.
+ * With SHD_ROUTE_DISPATCH a complete graph, or prefer-direct with an adjacent pair, gives the fold
+ * over the one direct edge (the lowest edge id joining the pair); on a complete graph no rows
+ * launch and no sweep run, and a pair without an edge is SHD_ROUTE_ENOEDGE.  A failed entry is
+ * NaN in every fold and never stops the rest; the code comes back at the end (shd_route_fold,
+ * shd_route_pair_fold) or by the next shd_route_sync (shd_route_fold_async).  A vertex out of
+ * range is SHD_ROUTE_EINVAL for the whole call; ns == 0 is SHD_ROUTE_OK.
+ *   Values: NaN is reserved for failed entries.  The two blocking calls scan val and return
+ * SHD_ROUTE_EINVAL, nothing written, if any value is NaN.  shd_route_fold_async does not look:
+ * a NaN value there gives unspecified entries on the paths that cross it, never a fault.
+ * +inf and -inf are ordinary values.
+ *   Exactness: every entry is a deterministic left fold from the source, acc = op(acc, a_e) hop
+ * by hop from the op's start value.  There are no atomics on values and nothing is reassociated,
+ * so all four ops are reproducible and equal the plain fold in double, bit for bit:
+ *   SUM over the edge latencies equals lat of shd_route_rows;
+ *   SUM over ones equals the hop count of shd_route_hops;
+ *   PROD over 1 - loss equals rel of shd_route_rows on graphs without vertex loss.
+ *   The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the hops calls' scratch: per source of a chunk an f64 distance row, a u32 parent row
+ * and an i32 hop row, chunks sized to SHD_ROUTE_HOPS_SCRATCH (1 GiB).  One workgroup per source
+ * sorts the reached vertices by hop depth once and sweeps the levels top-down once per fold;
+ * its state (14 bytes per vertex while n <= 65535, 16 above) lives in LDS or, on larger graphs
+ * and with SHD_ROUTE_FOLD_LDS=0, in HBM slices of 16 to 512 workgroup slots within 256 MiB,
+ * regrown (which synchronises the stream) when a launch needs more than the context holds.
+ * First use blocks only for what the hops calls build.  Diagnostic rate: every call runs the
+ * sources' SSSP. */
+#define SHD_ROUTE_FOLD_SUM  0   /* acc = acc + a_e, from 0.0 */
+#define SHD_ROUTE_FOLD_MIN  1   /* acc = a_e < acc ? a_e : acc, from +inf */
+#define SHD_ROUTE_FOLD_MAX  2   /* acc = a_e > acc ? a_e : acc, from -inf */
+#define SHD_ROUTE_FOLD_PROD 3   /* acc = acc * a_e, from 1.0 */
+#define SHD_ROUTE_FOLD_MAX_N 8  /* folds per call */
+/* Device pointers: d_val[nf * n_edges], d_out with ld >= nt and plane >= ns * ld; elements
+ * outside the nt entries of a row are never written. */
+int shd_route_fold_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                         int64_t ld, uint32_t flags, const int32_t* ops, int32_t nf, const double* d_val,
+                         double* d_out, int64_t plane, void* stream);
+/* Same with host pointers (ld = nt, plane = ns * nt); blocks. */
+int shd_route_fold(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                   uint32_t flags, const int32_t* ops, int32_t nf, const double* val, double* out);
+/* The sparse form: out[k * npairs + p] = fold k of (pair_src[p], pair_tgt[p]), in the caller's
+ * pair order; the pairs are grouped by source inside as shd_route_pair_loads groups them.  Host
+ * pointers; blocks. */
+int shd_route_pair_fold(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs,
+                        uint32_t flags, const int32_t* ops, int32_t nf, const double* val, double* out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

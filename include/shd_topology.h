@@ -45,6 +45,10 @@ typedef struct shd_graphml {
      * "" where a node has no <data>); NULL arrays when the key is not declared */
     int32_t has_vertex_str[SHD_VATTR_N];
     char** vertex_str[SHD_VATTR_N];
+    /* the jitter edge attribute (topology.c:1105-1114: validated, then unused), per edge id: NULL
+     * when no jitter key is declared for edges, NaN where an edge has no value and the key has no
+     * default */
+    double* edge_jitter;
 } shd_graphml_t;
 int shd_graphml_load(const char* path, shd_graphml_t* out, char* errbuf, size_t errlen);
 void shd_graphml_free(shd_graphml_t* g);
@@ -174,6 +178,23 @@ int shd_topology_link_loads(shd_topology_t* top, uint64_t* edge_packets, uint64_
  * zero before the first fill; each output may be NULL. */
 int shd_topology_ecmp_link_loads(shd_topology_t* top, double* edge_packets, double* transit_packets,
                                  uint64_t* unrouted);
+/* ---- path folds: a per-link quantity along the stored Paths ---------------------------------
+ * No reference equivalent (shd_route_pair_fold in shd_route.h).  Like the route calls above
+ * these run on engine 0 under the topology lock, compute on demand (diagnostic rate), cache
+ * nothing and change no accessor. */
+
+/* The graphml's jitter edge attribute, n_edges doubles in edge-id order (NaN where an edge has no
+ * value and the key no default).  SHD_ROUTE_EUNSUPPORTED for a topology whose graphml declares no
+ * jitter key for edges, or one made by shd_topology_new_from_graph. */
+int shd_topology_edge_jitter(shd_topology_t* top, double* out);
+/* out[p] = the fold op (SHD_ROUTE_FOLD_*) of edge_val[n_edges] along the route of the stored Path
+ * of {src[p], dst[p]}: the stored orientation (lower attached vertex -> higher) and the dispatch
+ * the cache used, exactly as shd_topology_get_path takes them.  Pairs the getters reject (not
+ * attached, never stored) and self pairs stored as the path to self give NaN.  A NaN in edge_val
+ * is SHD_ROUTE_EINVAL. */
+int shd_topology_fold_pairs(shd_topology_t* top, int32_t op, const double* edge_val, const int32_t* src,
+                            const int32_t* dst, int64_t npairs, double* out);
+
 /* One line per edge with a non-zero total, in edge-id order:
  *   link A<-->B (i<-->j) edge E is L ms with P loss, N packets
  * ("-->" on directed graphs; A, B = the edge's ends as the graph lists them, named as in the

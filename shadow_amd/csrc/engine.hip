@@ -28,6 +28,7 @@
 #include "link_loads.hpp"
 #include "path_ties.hpp"
 #include "ecmp_loads.hpp"
+#include "path_fold.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 #include "path_host.hpp"

@@ -304,7 +304,7 @@ int shd_graphml_load(const char* path, shd_graphml_t* out, char* errbuf, size_t 
     }
 
     /* _topology_checkGraphAttributes (topology.c:565-722): declared types + required keys */
-    int have_bwd = 0, have_bwu = 0, have_lat = 0, have_eloss = 0, have_vloss = 0;
+    int have_bwd = 0, have_bwu = 0, have_lat = 0, have_eloss = 0, have_vloss = 0, have_jitter = 0;
     for (int i = 0; i < nkeys && !rc; i++) {
         gkey* k = &keys[i];
         if (!k->name) continue;
@@ -326,7 +326,7 @@ int shd_graphml_load(const char* path, shd_graphml_t* out, char* errbuf, size_t 
             int want = 0;
             if (!strcmp(nmk, "latency")) { want = T_NUM; have_lat = 1; }
             else if (!strcmp(nmk, "packetloss")) { want = T_NUM; have_eloss = 1; }
-            else if (!strcmp(nmk, "jitter")) want = T_NUM;
+            else if (!strcmp(nmk, "jitter")) { want = T_NUM; have_jitter = 1; }
             if (want && k->type != want) {
                 seterr(errbuf, errlen, "edge attribute '%s' has an unsupported type", nmk);
                 rc = SHD_ROUTE_EINVAL;
@@ -376,6 +376,8 @@ int shd_graphml_load(const char* path, shd_graphml_t* out, char* errbuf, size_t 
         g->edge_packetloss = ea[EA_LOSS].a; ea[EA_LOSS].a = NULL;
         out->has_vertex_packetloss = have_vloss;
         if (have_vloss) { g->vertex_packetloss = va[VA_LOSS].a; va[VA_LOSS].a = NULL; }
+        /* validated above (topology.c:1105-1114); NaN where an edge has no value and the key no default */
+        if (have_jitter) { out->edge_jitter = ea[EA_JITTER].a; ea[EA_JITTER].a = NULL; }
         g->directed = directed;
         /* topology.c:769-790: prefix true/yes/1, case-insensitive */
         g->prefer_direct = prefer && (!strncasecmp(prefer, "true", 4) || !strncasecmp(prefer, "yes", 3) ||
@@ -414,6 +416,7 @@ void shd_graphml_free(shd_graphml_t* g) {
     free((void*)g->graph.edge_latency); free((void*)g->graph.edge_packetloss);
     free((void*)g->graph.vertex_packetloss);
     free(g->bandwidth_down); free(g->bandwidth_up);
+    free(g->edge_jitter);
     for (int a = 0; a < SHD_VATTR_N; a++) {
         if (g->vertex_str[a]) for (int32_t v = 0; v < g->graph.n_vertices; v++) free(g->vertex_str[a][v]);
         free(g->vertex_str[a]);

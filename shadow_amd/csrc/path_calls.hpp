@@ -1,7 +1,7 @@
 #pragma once
 // path_calls.hpp -- the path calls of the engine: hop counts and explicit routes
-// (path_hops.hpp), link loads (link_loads.hpp), the tie envelope (path_ties.hpp) and the ECMP
-// link loads (ecmp_loads.hpp), over one set of host stages.  What needs no device is
+// (path_hops.hpp), link loads (link_loads.hpp), path folds (path_fold.hpp), the tie envelope
+// (path_ties.hpp) and the ECMP link loads (ecmp_loads.hpp), over one set of host stages.  What needs no device is
 // path_host.hpp; here are the uploads, the launches and the entry points.  Not a stand-alone
 // header: engine.hip includes it once struct shd_route, hip_check, upload, DevBuf and
 // shd_route_rows_async are defined.
@@ -155,7 +155,7 @@ DevTies dev_ties(const shd_route* c) {
 
 // the buffers grown on demand (shd_route_destroy; the uploads are in the context's allocs)
 void path_free(PathDev& p) {
-    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.buf})
+    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.buf})
         if (q) (void)hipFree(q);
 }
 
@@ -586,6 +586,157 @@ int shd_route_pair_loads(shd_route_t* c, const int32_t* pair_src, const int32_t*
                               pair_wt ? dw.p : nullptr, flags)) ||
         (rc = sc.sync(c)) || (rc = out.finish(flags, edge_load_out, transit_out, unrouted_out)))
         return rc;
+    return sc.soft;
+}
+
+}  // extern "C"
+
+// ---- path folds ----
+namespace {
+
+// the ops of a call, by value for the kernel
+bool fold_ops_ok(const int32_t* ops, int32_t nf, FoldOps* out) {
+    if (!ops || nf < 1 || nf > SHD_ROUTE_FOLD_MAX_N) return false;
+    for (int k = 0; k < SHD_ROUTE_FOLD_MAX_N; k++) out->op[k] = SHD_ROUTE_FOLD_SUM;
+    for (int k = 0; k < nf; k++) {
+        if (ops[k] < SHD_ROUTE_FOLD_SUM || ops[k] > SHD_ROUTE_FOLD_PROD) return false;
+        out->op[k] = ops[k];
+    }
+    return true;
+}
+
+bool fold_has_nan(const double* val, size_t count) {
+    for (size_t q = 0; q < count; q++)
+        if (val[q] != val[q]) return true;
+    return false;
+}
+
+// the sweeps of k sources and their entries (fold_tree_kernel); HBM slices within 256 MiB, regrown
+// as the loads'
+int fo_tree(shd_route* c, const uint32_t* par, const int32_t* hrow, const int32_t* d_src, int k, const int32_t* d_tgt,
+            int nt, long long ld, const long long* d_eoff, const FoldOps& ops, int nf, const double* d_val, int mode,
+            double* d_out, long long plane, hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    if (mode != 2 && !c->path.fo_ready && fold_fits_lds(n)) {
+        int rc = hip_check(hipFuncSetAttribute((const void*)fold_tree_kernel<uint16_t, true, 1024>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldLdsBudget));
+        if (rc) return rc;
+        c->path.fo_ready = 1;
+    }
+    const char* e = getenv("SHD_ROUTE_FOLD_LDS");  // "0": the HBM form on graphs the LDS form takes
+    const StateLaunch f = state_form(n, mode, k, kFoSmall, FoldLayout<uint16_t>::make(n).total, kFoldLdsBudget,
+                                     knob_off(e), a16(FoldLayout<uint16_t>::make(n).total),
+                                     a16(FoldLayout<uint32_t>::make(n).total), (size_t)256 << 20);
+    return launch_state(c->path.fo_ws, f, st, [&](auto tag, char* ws, size_t stride) {
+        using F = decltype(tag);
+        hipLaunchKernelGGL((fold_tree_kernel<typename F::t, F::lds, 1024>), dim3(f.grid), dim3(1024), f.lds, st, g,
+                           par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, ops, nf, d_val, (long long)c->m, mode, d_out,
+                           plane, ws, stride, c->d_err);
+    });
+}
+
+// The nf folds of ns sources.  Entries as ld_sources takes them: the block, whose chunk i0
+// writes from row i0 of every plane on, or the sparse lists of d_eoff with absolute positions.
+int fo_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
+               const long long* d_eoff, const FoldOps& ops, int nf, const double* d_val, uint32_t flags, double* d_out,
+               long long plane, hipStream_t st) {
+    int rc = ensure_hops(c);
+    if (rc) return rc;
+    const int mode = hp_mode(c, flags);
+    return source_chunks(c, ns, mode, true, [&](int i0, int k, double* dist, uint32_t* par, int32_t* hrow) {
+        if (par && (rc = hp_trees(c, d_src + i0, k, dist, par, hrow, st))) return rc;
+        return fo_tree(c, par, hrow, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr, ops, nf, d_val, mode,
+                       d_eoff ? d_out : d_out + (long long)i0 * ld, plane, st);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_fold_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                         int64_t ld, uint32_t flags, const int32_t* ops, int32_t nf, const double* d_val,
+                         double* d_out, int64_t plane, void* stream) {
+    FoldOps fo;
+    if (!block_args_ok(c, d_src, ns, d_tgt, nt, ld) || !fold_ops_ok(ops, nf, &fo) || !d_val ||
+        plane < (int64_t)ns * ld || (ns && nt && !d_out))
+        return SHD_ROUTE_EINVAL;
+    if (ns == 0 || nt == 0) return SHD_ROUTE_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    return fo_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, fo, nf, d_val, flags, d_out, (long long)plane,
+                      (hipStream_t)stream);
+}
+
+int shd_route_fold(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
+                   const int32_t* ops, int32_t nf, const double* val, double* out) {
+    FoldOps fo;
+    if (!block_args_ok(c, src, ns, tgt, nt, nt) || !fold_ops_ok(ops, nf, &fo) || !val || (ns && nt && !out))
+        return SHD_ROUTE_EINVAL;
+    for (int32_t i = 0; i < ns; i++)
+        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
+    for (int32_t j = 0; j < nt; j++)
+        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
+    const size_t vals = (size_t)nf * (size_t)c->m;
+    if (fold_has_nan(val, vals)) return SHD_ROUTE_EINVAL;
+    if (ns == 0 || nt == 0) return SHD_ROUTE_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const size_t row_bytes = sizeof(double) * (size_t)nt;
+    const int32_t chunk = host_chunk(ns, row_bytes * nf);
+    const size_t dplane = (size_t)chunk * nt;  // one fold of a chunk on the device
+    DevBuf dv, dout;
+    int rc;
+    if ((rc = dv.alloc(sizeof(double) * vals)) || (rc = dout.alloc(sizeof(double) * dplane * nf))) return rc;
+    if (vals && hipMemcpy(dv.p, val, sizeof(double) * vals, hipMemcpyHostToDevice) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    return host_blocks(
+        c, src, ns, tgt, nt, chunk,
+        [&](int32_t, int32_t k, const int32_t* d_src, const int32_t* d_tgt) {
+            return shd_route_fold_async(c, d_src, k, d_tgt, nt, nt, flags, ops, nf, (const double*)dv.p, (double*)dout.p,
+                                        (int64_t)dplane, nullptr);
+        },
+        [&](int32_t i0, int32_t k) {
+            for (int f = 0; f < nf; f++)
+                if (int r = to_host(out + (size_t)f * ns * nt + (size_t)i0 * nt, (const double*)dout.p + f * dplane,
+                                    row_bytes * k))
+                    return r;
+            return SHD_ROUTE_OK;
+        });
+}
+
+int shd_route_pair_fold(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs,
+                        uint32_t flags, const int32_t* ops, int32_t nf, const double* val, double* out) {
+    FoldOps fo;
+    if (!pair_args_ok(c, pair_src, pair_tgt, npairs) || !pairs_in_range(c, pair_src, pair_tgt, (int)npairs) ||
+        !fold_ops_ok(ops, nf, &fo) || !val || (npairs && !out))
+        return SHD_ROUTE_EINVAL;
+    const size_t vals = (size_t)nf * (size_t)c->m;
+    if (fold_has_nan(val, vals)) return SHD_ROUTE_EINVAL;
+    const int np = (int)npairs;
+    if (np == 0) return SHD_ROUTE_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // the entries of distinct source u are the grouped positions first[u] .. first[u + 1]
+    const PairGroups pg = group_pairs(pair_src, pair_tgt, nullptr, np);
+    const int nu = (int)pg.us.size();
+    DevBuf dsrc, dtgt, doff, dv, dout;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
+        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) || (rc = dv.alloc(sizeof(double) * vals)) ||
+        (rc = dout.alloc(sizeof(double) * (size_t)np * nf)))
+        return rc;
+    if (hipMemcpy(dsrc.p, pg.us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, pg.gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(doff.p, pg.first.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        (vals && hipMemcpy(dv.p, val, sizeof(double) * vals, hipMemcpyHostToDevice) != hipSuccess))
+        return SHD_ROUTE_EDEVICE;
+    SoftCode sc;
+    std::vector<double> grouped((size_t)np * nf);
+    if ((rc = fo_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, 0, (const long long*)doff.p, fo, nf,
+                         (const double*)dv.p, flags, (double*)dout.p, (long long)np, nullptr)) ||
+        (rc = sc.sync(c)) || (rc = to_host(grouped.data(), dout.p, sizeof(double) * grouped.size())))
+        return rc;
+    // back to the caller's pair order
+    for (int f = 0; f < nf; f++)
+        for (int gq = 0; gq < np; gq++) out[(size_t)f * np + pg.order[gq]] = grouped[(size_t)f * np + gq];
     return sc.soft;
 }
 

@@ -97,7 +97,7 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 }
 
 // ---- the form of a per-source state kernel ----
-// hops_depth_kernel, loads_tree_kernel, ties_dag_kernel and ecmp_dag_kernel keep one source's
+// hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, ties_dag_kernel and ecmp_dag_kernel keep one source's
 // state per workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
@@ -155,6 +155,8 @@ struct PathDev {
     PathSlices hp_ws, ld_ws, ti_ws, ec_ws;
     char* buf = nullptr;  // the row scratch (scratch_chunks), grown on demand
     size_t buf_cap = 0;
+    PathSlices fo_ws;  // folds: the HBM slices, and
+    int fo_ready = 0;  // the LDS form's dynamic-LDS limit is raised
 };
 
 }  // namespace shd

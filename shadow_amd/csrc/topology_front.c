@@ -830,6 +830,51 @@ int shd_topology_ecmp_link_loads(shd_topology_t* t, double* edge_packets, double
     return rc;
 }
 
+/* ---- path folds along the stored Paths (shd_route_pair_fold on engine 0, nothing cached) ---- */
+
+int shd_topology_edge_jitter(shd_topology_t* t, double* out) {
+    if (!t || !out) return SHD_ROUTE_EINVAL;
+    if (!t->gml.edge_jitter) return SHD_ROUTE_EUNSUPPORTED;
+    memcpy(out, t->gml.edge_jitter, sizeof(double) * (size_t)t->g.n_edges);
+    return SHD_ROUTE_OK;
+}
+
+int shd_topology_fold_pairs(shd_topology_t* t, int32_t op, const double* edge_val, const int32_t* src,
+                            const int32_t* dst, int64_t npairs, double* out) {
+    if (!t || !edge_val || npairs < 0 || npairs > 0x7FFFFFFF || (npairs && (!src || !dst || !out)))
+        return SHD_ROUTE_EINVAL;
+    if (op < SHD_ROUTE_FOLD_SUM || op > SHD_ROUTE_FOLD_PROD) return SHD_ROUTE_EINVAL;
+    for (int32_t e = 0; e < t->g.n_edges; e++)
+        if (isnan(edge_val[e])) return SHD_ROUTE_EINVAL;
+    if (!npairs) return SHD_ROUTE_OK;
+    /* the stored pairs in their stored orientation (min -> max); the rest stay NaN */
+    int32_t* ps = malloc(sizeof(int32_t) * (size_t)npairs);
+    int32_t* pt = malloc(sizeof(int32_t) * (size_t)npairs);
+    int64_t* at = malloc(sizeof(int64_t) * (size_t)npairs);
+    double* val = malloc(sizeof(double) * (size_t)npairs);
+    int rc = ps && pt && at && val ? SHD_ROUTE_OK : SHD_ROUTE_ENOMEM;
+    int64_t np = 0;
+    for (int64_t p = 0; p < npairs && !rc; p++) {
+        pcache* c;
+        int32_t i, j;
+        out[p] = NAN;
+        if (entry_ij(t, src[p], dst[p], &c, &i, &j) < 0) continue;
+        ps[np] = src[p] < dst[p] ? src[p] : dst[p];
+        pt[np] = src[p] < dst[p] ? dst[p] : src[p];
+        at[np++] = p;
+    }
+    if (!rc && np) {
+        pthread_mutex_lock(&t->lock);
+        rc = shd_route_pair_fold(t->eng[0], ps, pt, np, SHD_ROUTE_DISPATCH, &op, 1, edge_val, val);
+        pthread_mutex_unlock(&t->lock);
+        /* ENOEDGE: a self pair without a self-loop, stored as the path to self: NaN */
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;
+        for (int64_t q = 0; q < np && !rc; q++) out[at[q]] = val[q];
+    }
+    free(ps); free(pt); free(at); free(val);
+    return rc;
+}
+
 int shd_topology_dump_link_loads(shd_topology_t* t, FILE* out) {
     if (!t || !out) return SHD_ROUTE_EINVAL;
     const int32_t m = t->g.n_edges;

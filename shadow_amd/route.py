@@ -29,6 +29,8 @@ REFRESH_ALL, REFRESH_MINE, REFRESH_JOBS = 0x1, 0x2, 0x4  # SHD_ROUTE_REFRESH_*
 PAYLOAD_LAT16 = 0x1
 FILL_LAT16 = 0x100
 LOADS_ADD = 0x400  # shd_route.h SHD_ROUTE_LOADS_ADD
+FOLD_SUM, FOLD_MIN, FOLD_MAX, FOLD_PROD = 0, 1, 2, 3  # SHD_ROUTE_FOLD_*
+FOLD_MAX_N = 8
 
 
 class RouteError(RuntimeError):
@@ -87,6 +89,7 @@ EXPORTS = (
     "shd_route_plan_jobs", "shd_route_loads_async", "shd_route_loads", "shd_route_pair_loads",
     "shd_route_ties_async", "shd_route_ties",
     "shd_route_ecmp_loads_async", "shd_route_ecmp_loads", "shd_route_pair_ecmp_loads",
+    "shd_route_fold_async", "shd_route_fold", "shd_route_pair_fold",
 )
 
 _lib = None
@@ -181,6 +184,12 @@ def load_library():
     L.shd_route_ecmp_loads.argtypes = [P, P, I32, P, I32, U32, P, P, P, P]
     L.shd_route_pair_ecmp_loads.restype = C.c_int
     L.shd_route_pair_ecmp_loads.argtypes = [P, P, P, P, I64, U32, P, P, P]
+    L.shd_route_fold_async.restype = C.c_int
+    L.shd_route_fold_async.argtypes = [P, P, I32, P, I32, I64, U32, P, I32, P, P, I64, P]
+    L.shd_route_fold.restype = C.c_int
+    L.shd_route_fold.argtypes = [P, P, I32, P, I32, U32, P, I32, P, P]
+    L.shd_route_pair_fold.restype = C.c_int
+    L.shd_route_pair_fold.argtypes = [P, P, P, I64, U32, P, I32, P, P]
     _lib = L
     return L
 
@@ -436,7 +445,67 @@ class RouteEngine:
         _check(rc, "shd_route_pair_ecmp_loads")
         return el, tr, int(un[0])
 
+    def _fold_args(self, ops, values):
+        o = np.ascontiguousarray(ops, np.int32).reshape(-1)
+        v = np.ascontiguousarray(values, np.float64)
+        if v.ndim == 1 and len(o) == 1:
+            v = v.reshape(1, -1)
+        if v.shape != (len(o), self.info["n_edges"]):
+            raise ValueError("values must be (ops, n_edges)")
+        return o, v
+
+    def fold(self, sources, targets, ops, values, dispatch: bool = True):
+        """shd_route_fold: the array (nf, sources, targets) of the folds ops[k] (FOLD_SUM, FOLD_MIN,
+        FOLD_MAX, FOLD_PROD; at most FOLD_MAX_N) of the per-edge values[k] (float64, (nf, n_edges),
+        no NaN) along every (source, target) path, each a left fold from the source.  A failed
+        entry is NaN in every fold; a missing self-loop or an unreachable target raises
+        RouteError with ``err.partial`` = the array."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        o, v = self._fold_args(ops, values)
+        out = np.empty((len(o), len(s), len(t)))
+        rc = load_library().shd_route_fold(self._h, _p(s), len(s), _p(t), len(t), DISPATCH if dispatch else 0,
+                                           _p(o), len(o), _p(v), _p(out))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_fold")
+            err.partial = out
+            raise err
+        _check(rc, "shd_route_fold")
+        return out
+
+    def pair_fold(self, pair_src, pair_tgt, ops, values, dispatch: bool = True):
+        """shd_route_pair_fold: as fold() for a list of (source, target) pairs in any order,
+        repeats allowed: the array (nf, pairs) in the caller's pair order."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        if len(s) != len(t):
+            raise ValueError("pair_src and pair_tgt differ in length")
+        o, v = self._fold_args(ops, values)
+        out = np.empty((len(o), len(s)))
+        rc = load_library().shd_route_pair_fold(self._h, _p(s), _p(t), len(s), DISPATCH if dispatch else 0,
+                                                _p(o), len(o), _p(v), _p(out))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_fold")
+            err.partial = out
+            raise err
+        _check(rc, "shd_route_pair_fold")
+        return out
+
     # -- device-pointer API (torch tensors as HBM plumbing) --------------------
+    def fold_async(self, d_src, d_tgt, ops, d_val, d_out, stream=None, dispatch=True, ld=None, plane=None):
+        """shd_route_fold_async over device tensors: int32 sources and targets, float64 values
+        (len(ops) x n_edges) and outputs (len(ops) planes of `plane` elements, rows of stride
+        ld); ops is a host sequence, read at call time."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        plane = ns * ld if plane is None else int(plane)
+        o = np.ascontiguousarray(ops, np.int32).reshape(-1)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_fold_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0, _p(o), len(o), ptr(d_val),
+            ptr(d_out), plane, C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_fold_async")
+
     def ecmp_loads_async(self, d_src, d_tgt, d_wt, d_edge_load, d_transit, d_unrouted, stream=None, dispatch=True,
                          ld=None, add=False):
         """shd_route_ecmp_loads_async over device tensors: int32 sources and targets, 64-bit

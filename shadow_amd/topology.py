@@ -31,6 +31,7 @@ EXPORTS = (
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
     "shd_topology_link_loads", "shd_topology_ecmp_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
+    "shd_topology_edge_jitter", "shd_topology_fold_pairs",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
@@ -42,7 +43,7 @@ class _GraphML(C.Structure):
     _fields_ = [("graph", _Graph), ("vertex_ids", C.POINTER(C.c_char_p)),
                 ("bandwidth_down", C.POINTER(C.c_double)), ("bandwidth_up", C.POINTER(C.c_double)),
                 ("has_vertex_packetloss", C.c_int32), ("has_vertex_str", C.c_int32 * 5),
-                ("vertex_str", C.POINTER(C.c_char_p) * 5)]
+                ("vertex_str", C.POINTER(C.c_char_p) * 5), ("edge_jitter", C.POINTER(C.c_double))]
 
 
 class TieStats(C.Structure):
@@ -115,6 +116,10 @@ def load_library():
     L.shd_topology_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_ecmp_link_loads.restype = C.c_int
     L.shd_topology_ecmp_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_edge_jitter.restype = C.c_int
+    L.shd_topology_edge_jitter.argtypes = [P, P]
+    L.shd_topology_fold_pairs.restype = C.c_int
+    L.shd_topology_fold_pairs.argtypes = [P, I32, P, P, P, C.c_int64, P]
     L.shd_topology_dump_link_loads.restype = C.c_int
     L.shd_topology_dump_link_loads.argtypes = [P, P]
     L.shd_topology_link_line.restype = C.c_int64
@@ -399,6 +404,35 @@ class Topology:
         if rc:
             raise RuntimeError(f"ecmp_link_loads failed ({rc})")
         return ep, tp, int(un.value)
+
+    def edge_jitter(self):
+        """shd_topology_edge_jitter: the graphml's jitter edge attribute per edge id (NaN where
+        an edge has none), or None for a topology without the key."""
+        L = load_library()
+        out = np.empty(int(L.shd_topology_edge_count(self._h)), np.float64)
+        rc = L.shd_topology_edge_jitter(self._h, C.c_void_p(out.ctypes.data))
+        if rc == -6:  # SHD_ROUTE_EUNSUPPORTED
+            return None
+        if rc:
+            raise RuntimeError(f"edge_jitter failed ({rc})")
+        return out
+
+    def fold_pairs(self, op, values, src, dst):
+        """shd_topology_fold_pairs: the fold `op` (route.FOLD_*) of the per-edge `values` along the
+        route of each pair's stored Path, NaN for the pairs the getters reject and for self
+        pairs stored as the path to self."""
+        L = load_library()
+        v = np.ascontiguousarray(values, np.float64)
+        s = np.ascontiguousarray(src, np.int32)
+        d = np.ascontiguousarray(dst, np.int32)
+        if len(v) != int(L.shd_topology_edge_count(self._h)) or len(s) != len(d):
+            raise ValueError("values must have one element per edge, src and dst one length")
+        out = np.empty(len(s), np.float64)
+        rc = L.shd_topology_fold_pairs(self._h, int(op), C.c_void_p(v.ctypes.data), C.c_void_p(s.ctypes.data),
+                                       C.c_void_p(d.ctypes.data), len(s), C.c_void_p(out.ctypes.data))
+        if rc:
+            raise RuntimeError(f"fold_pairs failed ({rc})")
+        return out
 
     def dump_link_loads(self, path: str):
         """shd_topology_dump_link_loads into the file `path`: one line per edge that carried
