@@ -323,6 +323,9 @@ DevDelta kd_args(const shd_route* c) {
     k.done = nullptr;
     // tests shrink the tie-event list to force the unseeded rerun of overflowing rows
     if (const char* e = getenv("SHD_ROUTE_EVCAP")) k.evcap = std::max(0, std::min(c->n, atoi(e)));
+    // and cap a chunk of phase A' at a few events, so that small graphs take several chunks
+    k.evchunk = 0;
+    if (const char* e = getenv("SHD_ROUTE_EVCHUNK")) k.evchunk = std::max(0, atoi(e));
     k.next = nullptr;
     k.stats = c->d_kd_stats;
     return k;

@@ -8,9 +8,13 @@
 // A  Delta-stepping.  Bucket k holds pending vertices with dist in [k*D, (k+1)*D).
 //    Pending vertices are a bitmask (u64 word per 64 vertices) plus, per word, a
 //    conservative lower bound of the pending distances (wmin), so a sweep opens only
-//    words that can hold bucket work.  Each sweep:
+//    words that can hold bucket work.  A sweep starts from the smallest pending distance,
+//    which 1024-thread rows do not scan for: every writer of wmin folds the value it leaves
+//    into the next sweep's slot (KDSmall::gmin) while the current sweep runs, and the first
+//    sweep's queue is the source alone.  Each sweep:
 //      gather  one thread per word moves the pending vertices with dist < T into a
-//              dense LDS queue (no atomics: nothing else runs);
+//              dense LDS queue (no atomics but the queue's tail and one min per wave:
+//              nothing else runs), one barrier after it;
 //      prep    one thread per queue entry loads its CSR row bounds (all loads in
 //              flight at once, so a sweep pays one global latency for them);
 //      expand  each wave takes a 64-entry slice (strided over the queue, so the BA
@@ -122,6 +126,8 @@ struct DevDelta {
     uint32_t* prow;                     // row store: parent records [slot * rstride + v]
     long long rstride;
     int evcap;                          // tie events per source held in the workgroup slice
+    int evchunk;                        // tests (SHD_ROUTE_EVCHUNK): tie events per chunk of phase A' at most
+                                        // (0: as many as half the LDS table holds)
     int* done;                          // per row-store slot: 1 once the kept row is complete
     int n, nw;
     int nlight;                         // light in-arcs
@@ -208,7 +214,10 @@ struct KDOut {
 };
 
 struct KDSmall {
-    unsigned gmin[2];   // min pending distance at the start of a bucket round (by parity)
+    unsigned gmin[2];   // min pending distance (min over wmin[]) at the start of a bucket round, by parity:
+                        // round r reads [par]; 1024-thread rows accumulate round r + 1's into [par ^ 1]
+                        // (the gather: what each word is left with; kd_relax_list: every nd it leaves
+                        // pending), smaller rows scan wmin[] into it at the round's top
     int head, tail;     // work queue of this bucket round: grabbed / reserved
     int busy;           // compute waves holding a grabbed slice
     int nexit;          // compute waves that left the async loop
@@ -320,6 +329,9 @@ constexpr int KD_MAXD = 32;           // phase C path walk: arcs held in registe
 #ifndef KD_BHELP
 #define KD_BHELP 1  // 1024-thread rows: B waves other than wave 0 take lat-row blocks once their fix-ups are done (0, at 4 B waves: 40.05-40.31 ms against 39.84-40.09)
 #endif
+#ifndef KD_ACCMIN_B
+#define KD_ACCMIN_B 1024  // phase A: rows of at least this many threads accumulate the next round's minimum and queue round 0's source directly; smaller rows scan wmin[] (one word per thread at C3: nothing to save) -- 0, three runs each on one box: C3 2.395-2.407 ms against the parent's 2.339, C4 the same as 1024
+#endif
 #ifndef KD_WQ_N
 #define KD_WQ_N 2
 #endif
@@ -334,7 +346,7 @@ constexpr int kd_rr() { return B >= 1024 ? KD_RR : 256; }
 // parent | ridx << 16 (| w << 24, packed arcs) of the parent arc (KD_SRC_MARK for the source)
 // | tie events
 // {p | ridx << 16 | w << 24, v} x n (seeded rows) | a second record slice u32[n + 8] (rows
-// alternate between the two).  Seeded rows use relv as u32 keys.
+// alternate between the two).
 __host__ __device__ inline size_t kd_ws_stride(int n) {
     return a16(sizeof(double) * n) + a16(sizeof(uint32_t) * (n + 8)) + a16(8 * (size_t)n) + 256 +
            a16(sizeof(uint32_t) * (n + 8));
@@ -444,8 +456,9 @@ __device__ inline void pop4(unsigned long long* b, int k, int v[4]) {
 // them out.  Called by a whole wave (ballots); `cnt` is wave-uniform.
 __device__ inline void kd_relax_list(const uint32_t* wimp, int cnt, int lane, unsigned long long upto,
                                      uint32_t* dist32, unsigned long long* pend, unsigned* wmin, uint16_t* ring,
-                                     int* tail, int rc, unsigned T, unsigned long long* sm_acc) {
+                                     int* tail, unsigned* gnext, int rc, unsigned T, unsigned long long* sm_acc) {
     __builtin_amdgcn_wave_barrier();
+    unsigned gm = 0xFFFFFFFFu;
     for (int b0 = 0; b0 < cnt; b0 += 64) {
         const bool act = b0 + lane < cnt;
         const uint32_t e = act ? wimp[b0 + lane] : 0u;
@@ -461,7 +474,8 @@ __device__ inline void kd_relax_list(const uint32_t* wimp, int cnt, int lane, un
             }
         }
         const bool push = won && nd < T;
-        if (won && nd >= T) { atomicOr(&pend[v >> 6], 1ull << (v & 63)); atomicMin(&wmin[v >> 6], nd); }
+        bool keep = won && nd >= T;  // stays pending: a far improvement, or a push that found the queue full
+        if (keep) { atomicOr(&pend[v >> 6], 1ull << (v & 63)); atomicMin(&wmin[v >> 6], nd); }
         const unsigned long long pm = __ballot(push);
         if (pm) {
             const int ctot = __popcll(pm);
@@ -473,12 +487,15 @@ __device__ inline void kd_relax_list(const uint32_t* wimp, int cnt, int lane, un
             const int rk = __popcll(pm & (upto >> 1));
             // one copy of the vertex: the queue's (else the pending bitmask)
             if (push && rk < qk) { ring[qb + rk] = (uint16_t)v; atomicAnd(&pend[v >> 6], ~(1ull << (v & 63))); }
-            if (push && rk >= qk) { atomicOr(&pend[v >> 6], 1ull << (v & 63)); atomicMin(&wmin[v >> 6], nd); }
+            if (push && rk >= qk) { keep = true; atomicOr(&pend[v >> 6], 1ull << (v & 63)); atomicMin(&wmin[v >> 6], nd); }
 #ifdef SHD_STAMPS
             if (lane == 0 && ctot > qk) atomicAdd(&sm_acc[14], (unsigned long long)(ctot - qk));
 #endif
         }
+        // every write of wmin is folded into the next round's minimum (see the round's top)
+        gm = min(gm, keep ? nd : 0xFFFFFFFFu);
     }
+    if (gnext && __ballot(gm != 0xFFFFFFFFu)) { gm = kd_wave_min_dpp(gm); if (lane == 0) atomicMin(gnext, gm); }
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -1410,7 +1427,105 @@ __device__ __attribute__((noinline)) void kd_fixup(const int s_, KD_GLOBAL uint3
     }
 }
 
-#define KD_KERNEL_PARAMS                                                                              \
+// Phase A' of a seeded row: the parents of the vertices that kept D0.  Such a vertex holds the
+// seed-derived parent from the init pass; a tight improved in-neighbour reported as a tie
+// event may beat it (tie rule: largest w, then smallest parent): keys (255 - w) << 24 |
+// parent << 8 | ridx, min over that parent and every valid event.  Each event is evaluated
+// once: it is valid if v kept D0 and the arc is tight; its key is compared with the key of v's
+// present record, and the events that beat it are min-combined per vertex in an open-addressed
+// LDS table {vertex, key} over phase A's work area (queue + record ring: dead here, written
+// before it is read by phases B/C, re-initialised by the next row).  Then one store per table
+// entry: exactly the vertices whose record changes.  A claim is one atomicCAS on the vertex
+// word (empty, or already v) with linear probing, at most H probes: a chunk holds at most
+// H / 2 events, so a free slot exists, and no thread waits for another.  Rows with more events
+// than that take chunks: after a chunk's stores have drained, the next chunk's base is the
+// updated record, itself a valid tight arc of v, so the minimum over the chunks is the minimum
+// over all events.  Called by every thread of the workgroup (barriers inside).  Not inlined:
+// its registers are allocated for these loops alone, as kd_output's.
+template <int B>
+__device__ __attribute__((noinline)) void kd_events(KD_GLOBAL uint32_t* __restrict__ const wpr,
+                                                    const KD_GLOBAL kd_u2* __restrict__ const evl, const int nev,
+                                                    const int evchunk, int* __restrict__ const err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RR = kd_rr<B>();
+    KDSmall* sm = reinterpret_cast<KDSmall*>(smem);
+    const int n = kd_uni(sm->out.n), rc = kd_uni(sm->out.rc);
+    const KDLayout<B> L = KDLayout<B>::make(n, rc, RR);
+    const int tid = threadIdx.x;
+    const uint16_t* dist = reinterpret_cast<const uint16_t*>(smem + L.dist);
+    // the current job's seeds: D0(v) = min_j w(s,u_j) + d_{u_j}(v), saturating at 0xFFFF
+    const int nseed = kd_uni(sm->job.nseed);
+    const KD_GLOBAL uint16_t* const drow = (const KD_GLOBAL uint16_t*)kd_uni(sm->drow);
+    const long long rstride = kd_uni(sm->rstride);
+    const KD_GLOBAL uint16_t* sdrow[KD_SEEDS];
+    unsigned wsu[KD_SEEDS];
+#pragma unroll
+    for (int q = 0; q < KD_SEEDS; q++) {
+        sdrow[q] = drow + (size_t)kd_uni(q < nseed ? sm->job.seed[q] : 0) * rstride;
+        wsu[q] = (unsigned)kd_uni(q < nseed ? sm->job.wr[q] : 0) & 0xFFFFu;
+    }
+    uint32_t* const tv = reinterpret_cast<uint32_t*>(smem + L.work);
+    const size_t wbytes = a16(2 * (size_t)rc) + 8 * (size_t)RR;
+    const int hmax = 31 - __clz((int)(wbytes >> 3));  // 2^hmax slots of 8 bytes fit
+    int chunk = 1 << (hmax - 1);
+    if (evchunk > 0) chunk = min(chunk, evchunk);  // (tests: several chunks on small graphs)
+    // this row's table: the smallest power of two >= 2 x its largest chunk
+    const int hb = max(1, min(hmax, 32 - __clz(2 * min(nev, chunk) - 1)));
+    const int H = 1 << hb;
+    uint32_t* const tk = tv + H;
+#ifdef SHD_STAMPS
+    if (tid == 0) sm->acc[34] += (unsigned long long)nev;
+#endif
+    for (int c0 = 0; c0 < nev; c0 += chunk) {
+        const int c1 = min(nev, c0 + chunk);
+        for (int t = tid; t < H; t += B) { tv[t] = 0xFFFFFFFFu; tk[t] = 0xFFFFFFFFu; }
+        lds_barrier();
+        for (int e = c0 + tid; e < c1; e += B) {
+            const kd_u2 r = evl[e];
+            const int v = (int)r.y;
+            const int p = (int)(r.x & 0xFFFFu);
+            const unsigned w = r.x >> 24, dv = ld16(dist, v);
+            // v's present record, from L2: the init's, the writer wave's, or an earlier
+            // chunk's (stored by another wave of this workgroup)
+            const uint32_t b = __hip_atomic_load(&wpr[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned d0 = 0xFFFFu;
+#pragma unroll
+            for (int q = 0; q < KD_SEEDS; q++)
+                if (q < nseed) d0 = min(d0, min(0xFFFFu, wsu[q] + (unsigned)sdrow[q][v]));
+            if (dv != d0 || ld16(dist, p) + w != dv) continue;  // v improved on D0, or the arc is not tight
+            const uint32_t ke = ((0xFFu - w) << 24) | ((uint32_t)p << 8) | ((r.x >> 16) & 0xFFu);
+            const unsigned pb = b & 0xFFFFu, wb = dv - ld16(dist, (int)pb);
+            const uint32_t kb = ((0xFFu - wb) << 24) | (pb << 8) | ((b >> 16) & 0xFFu);
+#ifdef SHD_STAMPS
+            atomicAdd(&sm->acc[35], 1ull);
+#endif
+            if (ke >= kb) continue;
+            unsigned h = ((unsigned)v * 0x9E3779B1u) >> (32 - hb);
+            int pr = 0;
+            for (; pr < H; pr++) {
+                const uint32_t old = atomicCAS(&tv[h], 0xFFFFFFFFu, (uint32_t)v);
+                if (old == 0xFFFFFFFFu || old == (uint32_t)v) { atomicMin(&tk[h], ke); break; }
+                h = (h + 1) & (unsigned)(H - 1);
+            }
+            if (pr >= H) raise_err(err, SHD_ROUTE_EDEVICE);  // (cannot happen: at most H / 2 entries)
+        }
+        lds_barrier();
+        for (int t = tid; t < H; t += B) {
+            const uint32_t v = tv[t];
+            if (v != 0xFFFFFFFFu) {
+                const uint32_t k = tk[t];
+                wpr[v] = ((k >> 8) & 0xFFFFu) | ((k & 0xFFu) << 16) | ((0xFFu - (k >> 24)) << 24);
+#ifdef SHD_STAMPS
+                atomicAdd(&sm->acc[30], 1ull);
+#endif
+            }
+        }
+        wait_stores();
+        lds_barrier();
+    }
+}
+
+#define KD_KERNEL_PARAMS                                                                         \
     DevDelta g, const int* __restrict__ src, int ns, const int* __restrict__ tgt, int nt, long long ld,     \
         double* __restrict__ lat_out, double* __restrict__ rel_out, double* __restrict__ row_min,          \
         int* __restrict__ err, char* __restrict__ ws, size_t ws_stride
@@ -1445,6 +1560,7 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(g.orec), (short)0, g.nnz * 4, 0x00020000);
     const int rc = g.rc;
     constexpr int NW = B / 64;
+    constexpr bool accmin = B >= KD_ACCMIN_B;  // the next round's minimum accumulated, not scanned for
     const bool writer = wid == NW - 1;  // drains parent records; never waits on a global load
     double* relv = reinterpret_cast<double*>(ws + (size_t)blockIdx.x * ws_stride);
     uint32_t* const wslice = reinterpret_cast<uint32_t*>(ws + (size_t)blockIdx.x * ws_stride + a16(sizeof(double) * n));
@@ -1661,7 +1777,8 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         for (int q = tid; q < RR; q += B) rrec[q] = make_uint2(0u, 0xFFFFFFFFu);  // phases B/C reuse the area
         if (lane < 2 * KD_P) wmark[lane] = 0u;  // phase C reuses it
         if (tid == 0) {
-            sm->gmin[0] = sm->gmin[1] = 0xFFFFFFFFu;
+            sm->gmin[0] = accmin ? 0u : 0xFFFFFFFFu;  // (round 0's minimum: the source, at distance 0)
+            sm->gmin[1] = 0xFFFFFFFFu;
             sm->rtail = sm->rdone = 0;
             sm->nev = 0; sm->evovf = 0;
             if constexpr (B >= 1024) {  // the split region's: the lat row's minimum (the previous row's
@@ -1675,8 +1792,10 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         KD_STAMP(0);  // after the seed wait and the distance init
         if (tid == 0) {
             dist[s] = 0;
-            pend[s >> 6] = 1ull << (s & 63);
-            wmin[s >> 6] = 0;
+            if constexpr (!accmin) {
+                pend[s >> 6] = 1ull << (s & 63);
+                wmin[s >> 6] = 0;
+            }
         }
         lds_barrier();
 
@@ -1692,28 +1811,50 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
         int par = 0;
         const int ncomp = NW - 1;
         int wnev = 0;  // writer wave: tie events stored so far
+        // Rows of KD_ACCMIN_B threads and more (`accmin`; smaller rows scan wmin[] at the round's
+        // top, one word per thread) do not scan for the round's minimum, and round 0 takes its
+        // queue, the source alone, from thread 0 instead of a gather that would find one bit.
+        // Invariant: at the barrier that ends round r,
+        // gmin[par ^ 1] = min over k of wmin[k], which is what round r + 1 starts from.  Every
+        // writer of wmin folds the value it leaves into that slot: the init (gmin[0] = 0: the
+        // source), the gather (each word's value after it: `rest` where it opened the word, the
+        // untouched bound elsewhere; one atomicMin per wave) and the two atomicMin(&wmin[..], nd)
+        // of kd_relax_list (the same nd).  wmin stays a lower bound that may be stale-low (a
+        // vertex improved again and left through the queue): that costs one empty gather, which
+        // leaves the word's bound exact, as it did under the scan.  Thread 0 resets the other
+        // slot before the round's first barrier; nothing writes it before that barrier.
+        bool round0 = accmin;
         KD_MARK();
         for (;;) {
             KD_COUNT(5, tid == 0 ? 1 : 0);
-            {
+            if constexpr (!accmin) {
                 unsigned m0 = 0xFFFFFFFFu;
                 for (int k = tid; k < nw; k += B) m0 = min(m0, wmin[k]);
                 const unsigned wm = kd_wave_min_dpp(m0);
                 if (lane == 0 && wm != 0xFFFFFFFFu) atomicMin(&sm->gmin[par], wm);
             }
             for (int q = tid; q < rc; q += B) ring[q] = 0xFFFFu;
-            if (tid == 0) { sm->gmin[par ^ 1] = 0xFFFFFFFFu; sm->head = sm->tail = 0; sm->busy = 0; sm->nexit = 0; }
+            if (tid == 0) {
+                sm->gmin[par ^ 1] = 0xFFFFFFFFu; sm->head = sm->tail = 0; sm->busy = 0; sm->nexit = 0;
+                // round 0's queue is the source alone (thread 0 reset ring[0] itself, above)
+                if (round0) { ring[0] = (uint16_t)s; sm->tail = 1; }
+            }
             lds_barrier();
             const unsigned m = sm->gmin[par];
             if (m == 0xFFFFFFFFu) break;
             if (m >= T) T = (m / delta + 1) * delta;
             KD_ACC(11);
             // gather: pending vertices with dist < T into the queue (one thread per word)
+            // (and the next round's minimum: what each word's bound is left at)
+            unsigned gnext = 0xFFFFFFFFu;
+            if (!round0) {
             for (int k0 = 0; k0 < nw; k0 += B) {
                 const int k = k0 + tid;
                 unsigned long long bits = 0ull, take = 0ull;
                 unsigned rest = 0xFFFFFFFFu;
-                const bool act = k < nw && wmin[k] < T;
+                const unsigned wk = k < nw ? wmin[k] : 0xFFFFFFFFu;
+                const bool act = wk < T;
+                if (!act) gnext = min(gnext, wk);
                 if (act) {
                     bits = pend[k];
                     unsigned long long b = bits;
@@ -1755,11 +1896,18 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
                     }
                     pend[k] = bits & ~take;
                     wmin[k] = rest;
+                    gnext = min(gnext, rest);
                 }
             }
+            if constexpr (accmin) {
+                const unsigned wm = kd_wave_min_dpp(gnext);
+                if (lane == 0 && wm != 0xFFFFFFFFu) atomicMin(&sm->gmin[par ^ 1], wm);
+            }
+            // tail may stand past rc (entries gathered past capacity stayed pending): every
+            // reader takes min(tail, rc), every pusher rc - its own reservation
             lds_barrier();
-            if (tid == 0) sm->tail = min(sm->tail, rc);
-            lds_barrier();
+            }
+            round0 = false;
             KD_ACC(8);
             if (!writer) {
                 // ---- compute wave: pull slices until the round drains ----------------
@@ -1969,7 +2117,7 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
                         static_assert(KD_IMP >= 192, "two steps between flush checks");
                         auto flush = [&]() __attribute__((always_inline)) {
                             kd_relax_list(wimp, nimp, lane, upto, reinterpret_cast<uint32_t*>(dist), pend, wmin, ring,
-                                          &sm->tail, rc, T, KD_ACCP);
+                                          &sm->tail, accmin ? &sm->gmin[par ^ 1] : nullptr, rc, T, KD_ACCP);
                             nimp = 0;
                         };
                         if (b0 + 64 * KD_P <= total) {
@@ -2000,7 +2148,7 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
                         process(wb, b0);
                         b0 += 64 * KD_P;
                     }
-                    if (nimp) kd_relax_list(wimp, nimp, lane, upto, reinterpret_cast<uint32_t*>(dist), pend, wmin, ring, &sm->tail, rc, T, KD_ACCP);
+                    if (nimp) kd_relax_list(wimp, nimp, lane, upto, reinterpret_cast<uint32_t*>(dist), pend, wmin, ring, &sm->tail, accmin ? &sm->gmin[par ^ 1] : nullptr, rc, T, KD_ACCP);
 #ifdef SHD_STAMPS
                     if (tid == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); sm->acc[23] += t_ - ks0; ks0 = t_; sm->acc[25] += (total + 64 * KD_P - 1) / (64 * KD_P); }
 #endif
@@ -2112,57 +2260,8 @@ __device__ __attribute__((always_inline)) inline void kd_rows_body(KD_KERNEL_PAR
                 goto kd_restart;
             }
             uint32_t* const wpr = wpr_of();
-            SEED_VIEW();
-            auto d0 = [&](int v) __attribute__((always_inline)) {
-                unsigned x = 0xFFFFu;
-#pragma unroll
-                for (int q = 0; q < KD_SEEDS; q++)
-                    if (q < nseed) x = min(x, min(0xFFFFu, wsu[q] + (unsigned)sdrow[q][v]));
-                return x;
-            };
             KD_ACC(27);
-            // a vertex that kept D0 holds the seed-derived parent from the init pass; a tight
-            // improved in-neighbour reported as a tie event may beat it (tie rule: largest w,
-            // then smallest parent): keys (255 - w) << 24 | parent << 8 | ridx, min over
-            // that parent and every valid event, through u32 keys in the slice (relv is free)
-            uint32_t* key = reinterpret_cast<uint32_t*>(relv);
-            // event e -> v (-1 if invalid: v improved on D0, or the arc is not tight) + key
-            auto event = [&](int e, int& v, uint32_t& ke) __attribute__((always_inline)) {
-                const uint2 r = evl[e];
-                v = (int)r.y;
-                const int p = (int)(r.x & 0xFFFFu);
-                const unsigned w = r.x >> 24, dv = ld16(dist, v);
-                if (dv != d0(v) || ld16(dist, p) + w != dv) { v = -1; return; }
-                ke = ((0xFFu - w) << 24) | ((uint32_t)p << 8) | ((r.x >> 16) & 0xFFu);
-            };
-            for (int e = tid; e < nev; e += B) {
-                int v; uint32_t ke = 0;
-                event(e, v, ke);
-                if (v >= 0) {  // u's parent (from the copy above) as the starting key
-                    const uint32_t b = wpr[v];
-                    const unsigned pb = b & 0xFFFFu, wb = ld16(dist, v) - ld16(dist, (int)pb);
-                    key[v] = ((0xFFu - wb) << 24) | (pb << 8) | ((b >> 16) & 0xFFu);
-                }
-            }
-            wait_stores();
-            lds_barrier();
-            for (int e = tid; e < nev; e += B) {
-                int v; uint32_t ke = 0;
-                event(e, v, ke);
-                if (v >= 0) atomicMin(&key[v], ke);
-            }
-            wait_stores();
-            lds_barrier();
-            for (int e = tid; e < nev; e += B) {
-                int v; uint32_t ke = 0;
-                event(e, v, ke);
-                if (v >= 0) {
-                    const uint32_t k = __hip_atomic_load(&key[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    wpr[v] = ((k >> 8) & 0xFFFFu) | ((k & 0xFFu) << 16) | ((0xFFu - (k >> 24)) << 24);
-                }
-            }
-            wait_stores();
-            lds_barrier();
+            kd_events<B>((KD_GLOBAL uint32_t*)wpr, (const KD_GLOBAL kd_u2*)evl, nev, g.evchunk, err);
             KD_ACC(28);
         }
         KD_STAMP(1);

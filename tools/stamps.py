@@ -102,12 +102,11 @@ if eng.info["kernel"] == 4:
     ns0 = max(d[:, 26].mean(), 1)
     print(f"  wave0 slices {ns0:.0f}: setup {d[:, 22].mean() / ns0:.0f}  groups {d[:, 23].mean() / ns0:.0f} ({d[:, 25].mean() / ns0:.2f} groups/slice)  records {d[:, 24].mean() / ns0:.0f} cyc/slice")
     ng = max(d[:, 25].mean(), 1)
-    print(f"  wave0 per group: owners {d[:, 30].mean() / ng:.0f}  owners+loads {d[:, 27].mean() / ng:.0f}  process {d[:, 28].mean() / ng:.0f} (relax {d[:, 29].mean() / ng:.0f}) cyc")
     print(f"  queue overflow/source: pushes to pending {d[:, 14].mean():.0f}  gathered past capacity {d[:, 15].mean():.0f}")
     print(f"  drain of the previous row's stores {d[:, 9].mean():.0f}")
     print(f"  seeded init {d[:, 29].mean():.0f} (seed wait {d[:, 31].mean():.0f}, {100 * d[:, 31].mean() / max(d[:, 29].mean(), 1):.0f}% of it; "
           f"seeds dropped {d[:, 36].mean():.3f}/row)  A' copy {d[:, 27].mean():.0f}  A' events {d[:, 28].mean():.0f} cyc/source")
-    for k, nm in [(11, "minreduce"), (8, "gather"), (9, "prep"), (10, "expand"), (16, "B.short"), (17, "B.long"),
+    for k, nm in [(11, "round top"), (8, "gather"), (9, "prep"), (10, "expand"), (16, "B.short"), (17, "B.long"),
                   (18, "lat row+drain"), (19, "par copy"), (13, "C.compute")]:
         print(f"  A.{nm:10s} mean {d[:, k].mean():10.0f} cyc  ({d[:, k].mean() / max(d[:, 5].mean(), 1):.0f}/sweep)")
     if eng.info["block"] >= 1024:
@@ -117,8 +116,11 @@ if eng.info["kernel"] == 4:
         print(f"  split region: wave 0 B {d[:, 16].mean() + d[:, 17].mean():.0f} (p50 {np.median(d[:, 16] + d[:, 17]):.0f})  |  store wave: "
               f"distance row {d[:, 37].mean():.0f}  lat row {d[:, 38].mean():.0f}  |  wave 0 waits at the join {d[:, 39].mean():.0f} "
               f"(p50 {np.median(d[:, 39]):.0f}) cyc/row")
-    print(f"  pre-init: walk (wave 0) {d[:, 32].mean():.0f}  barrier wait {d[:, 33].mean():.0f}  pre-init wave {d[:, 34].mean():.0f} cyc/row; "
-          f"rows started pre-initialised {d[:, 35].sum():.0f} of {len(d)}")
+    # phase A' (seeded rows): tie events the writer wave logged, those that are valid (v kept D0 and
+    # the arc is tight), and the vertices whose record an event changed (one store each)
+    ev = d[:, 34]
+    print(f"  tie events/row: logged {ev.mean():.1f} (p50 {np.median(ev):.0f} p99 {np.percentile(ev, 99):.0f} max {ev.max()})  "
+          f"valid {d[:, 35].mean():.1f}  records changed {d[:, 30].mean():.1f}")
     t0 = d[:, 0] - d[:, 0].min()
     print(f"  start spread (cyc): p50 {np.median(t0):.0f} max {t0.max()}  end max {(d[:, 4] - d[:, 0].min()).max()}")
     sys.exit(0)
