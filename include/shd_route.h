@@ -125,12 +125,21 @@ typedef struct shd_graph {
     int32_t n_edges;
     const int32_t* edge_src;          /* [n_edges] */
     const int32_t* edge_dst;          /* [n_edges] */
-    const double* edge_latency;       /* [n_edges] ms, > 0        (topology.c:1070) */
+    const double* edge_latency;       /* [n_edges] ms, > 0        (topology.c:1070); no latency so small
+                                       * that a distance could absorb it: see below */
     const double* edge_packetloss;    /* [n_edges] in [0,1]       (topology.c:1090) */
     const double* vertex_packetloss;  /* [n_vertices] or NULL; NaN = absent (topology.c:330-347) */
     int32_t directed;                 /* graphml edgedefault="directed" */
     int32_t prefer_direct;            /* graph attribute preferdirectpaths (topology.c:761-790) */
 } shd_graph_t;
+/* Absorbed latencies.  Every call takes fl(d[u] + w) > d[u] for granted: an arc u -> v is on a
+ * shortest path exactly when d[u] + w == d[v] in f64, and those arcs must form a DAG.  With
+ * min_w and max_w the smallest and the largest latency over the edges that are no self-loops,
+ * shd_route_create refuses a graph with min_w <= (n_vertices - 1) * max_w * 2^-52 with
+ * SHD_ROUTE_EUNSUPPORTED, from its host validation, before it touches the device.  (No distance
+ * exceeds (n - 1) max_w (1 + 2^-53)^n, ulp(d) <= d 2^-52, and absorption needs w <= ulp(d) / 2:
+ * the factor of two left over covers the rounding growth of the fold.  50,000 vertices with
+ * latencies up to 250 ms: latencies of 3e-9 ms and below are refused.) */
 
 typedef struct shd_route_info {
     int32_t n_vertices;

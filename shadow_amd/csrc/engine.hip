@@ -490,18 +490,27 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
     if (n <= 0 || m < 0 || (m > 0 && (!g->edge_src || !g->edge_dst || !g->edge_latency || !g->edge_packetloss)))
         return SHD_ROUTE_EINVAL;
     // validation as topology.c:1041-1124 (edges) and 811-978 (vertex packetloss)
+    double arc_min = INFINITY, arc_max = 0.0;  // over the edges that are relaxed (no self-loops)
     for (int e = 0; e < m; e++) {
         int a = g->edge_src[e], b = g->edge_dst[e];
         double w = g->edge_latency[e], p = g->edge_packetloss[e];
         if (a < 0 || a >= n || b < 0 || b >= n) return SHD_ROUTE_EINVAL;
         if (!(w > 0.0) || std::isinf(w)) return SHD_ROUTE_EINVAL;
         if (!(p >= 0.0 && p <= 1.0)) return SHD_ROUTE_EINVAL;
+        if (a != b) { arc_min = std::min(arc_min, w); arc_max = std::max(arc_max, w); }
     }
     if (g->vertex_packetloss)
         for (int v = 0; v < n; v++) {
             double p = g->vertex_packetloss[v];
             if (!std::isnan(p) && !(p >= 0.0 && p <= 1.0)) return SHD_ROUTE_EINVAL;
         }
+    // No latency may be absorbed: every kernel and path call takes d[u] + w > d[u] for granted
+    // (the tight arcs d[u] + w == d[v] form a DAG, a parent is strictly nearer than its child).
+    // A distance is a left fold of at most n - 1 latencies, so no d exceeds (n - 1) max_w times
+    // (1 + 2^-53)^n; ulp(d) <= d 2^-52, and fl(d + w) == d needs w <= ulp(d) / 2.  Refusing
+    // min_w <= (n - 1) max_w 2^-52 therefore keeps a factor of two, which covers the rounding
+    // growth of the fold.  (C4f: 50,000 vertices, latencies up to ~250 ms: refused below 3e-9 ms.)
+    if (arc_max > 0.0 && arc_min <= (double)(n - 1) * (arc_max * 0x1p-52)) return SHD_ROUTE_EUNSUPPORTED;
     if (hipSetDevice(device) != hipSuccess) return SHD_ROUTE_EDEVICE;
 
     shd_route* c = new (std::nothrow) shd_route();

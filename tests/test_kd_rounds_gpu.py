@@ -122,6 +122,40 @@ def test_no_context_holds_an_unreachable_component(kd):
         route.RouteEngine(g)
 
 
+def test_no_context_holds_an_absorbed_latency(kd):
+    """Every kernel takes fl(d[u] + w) > d[u] for granted (include/shd_route.h, "Absorbed
+    latencies"): shd_route_create refuses min_w <= (n - 1) max_w 2^-52 over the edges that are no
+    self-loops with SHD_ROUTE_EUNSUPPORTED, at the threshold itself too, and takes the graphs just
+    on the other side of it, a tiny self-loop latency among them.  Contexts are made and closed;
+    nothing is launched on any of these graphs."""
+    from shadow_amd import route
+    from tests import frac_graphs as fg
+    from tests.test_frac_graphs import chain
+    a = _graph("ba400")
+    nl = a.src != a.dst
+    e = int(np.flatnonzero(nl)[7])
+
+    def with_latency(w, at=e):
+        lat = a.latency.copy()
+        lat[at] = w
+        return Graph(n=a.n, src=a.src, dst=a.dst, latency=lat, packetloss=a.packetloss,
+                     vertex_packetloss=a.vertex_packetloss, directed=a.directed, name="ba400_tiny")
+
+    thr = (a.n - 1) * (float(a.latency[nl].max()) * 2.0 ** -52)
+    up = float(np.nextafter(thr, 1.0))
+    for g in (with_latency(thr), with_latency(thr / 3), with_latency(5e-324), chain(1e-17), chain(3 * 2.0 ** -52)):
+        assert fg.absorbs(g)
+        with pytest.raises(route.RouteError) as ei:
+            route.RouteEngine(g)
+        assert ei.value.code == route.EUNSUPPORTED
+    loop = int(np.flatnonzero(~nl)[0])
+    for g in (with_latency(up), with_latency(1e-300, at=loop), chain(float(np.nextafter(3 * 2.0 ** -52, 1.0))), chain(1e-3)):
+        assert not fg.absorbs(g)
+        eng = route.RouteEngine(g)
+        assert eng.info["n_vertices"] == g.n
+        eng.close()
+
+
 @pytest.mark.parametrize("seeds", ["1", "2", "3"])
 @pytest.mark.parametrize("evcap", [None, "2"])
 @pytest.mark.parametrize("evchunk", [None, "1", "8"])

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from shadow_amd.graph import Graph, config
+from tests import frac_graphs as fgr
 from tests import shape_graphs as sg
 from tests import stream_order as so
 from tests import test_hops_gpu as hg
@@ -88,6 +89,8 @@ def graph(name):
         return sg.sized(int(name[5:]))
     if name in sg.SUITE:
         return sg.get(name)
+    if name in fgr.SUITE:
+        return fgr.get(name)
     return hg._graph(name)[0]
 
 
