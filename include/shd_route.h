@@ -14,7 +14,8 @@
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
  * rows launch inside and fall under the same rule, and so do the tie envelope calls
  * (shd_route_ties*), the ECMP link loads calls (shd_route_ecmp_loads*,
- * shd_route_pair_ecmp_loads) and the path fold calls (shd_route_fold*, shd_route_pair_fold).
+ * shd_route_pair_ecmp_loads), the path fold calls (shd_route_fold*, shd_route_pair_fold) and
+ * the link loss calls (shd_route_loss*, shd_route_pair_loss).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -38,13 +39,15 @@
  *                  shd_route_fw_table_async (the dense tables, built on the host and copied);
  *                  the hops, loads, folds, ties and ECMP loads calls (their in-CSR with edge ids; the
  *                  ties and ECMP loads calls also their per-arc reliabilities and out-CSR, the
- *                  ECMP loads calls the out-arcs' edge ids); all once per context
+ *                  ECMP loads calls the out-arcs' edge ids; the loss calls also their per-edge
+ *                  and per-vertex loss columns); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
  *                  the hops, loads, folds, ties and ECMP loads calls when their source chunk
- *                  grows, shd_route_loads_async, shd_route_fold_async, shd_route_ties_async and
- *                  shd_route_ecmp_loads_async in their HBM forms when the slices grow (those
+ *                  grows (the loss calls follow the loads calls), shd_route_loads_async,
+ *                  shd_route_fold_async, shd_route_ties_async, shd_route_ecmp_loads_async and
+ *                  shd_route_loss_async in their HBM forms when the slices grow (those
  *                  synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
@@ -80,6 +83,9 @@
  *   shd_route_fold, shd_route_pair_fold <- (no reference equivalent; any per-link quantity
  *                         folded along the chosen paths, e.g. the jitter edge attribute the
  *                         reference validates and drops, topology.c:1105-1114)
+ *   shd_route_loss, shd_route_pair_loss <- (no reference equivalent; the reference drops a
+ *                         packet with one end-to-end coin flip on the Path's reliability and
+ *                         cannot say on which link or router it was lost)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -454,6 +460,85 @@ int shd_route_fold(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32
  * pointers; blocks. */
 int shd_route_pair_fold(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt, int64_t npairs,
                         uint32_t flags, const int32_t* ops, int32_t nf, const double* val, double* out);
+
+/* ---- link loss: expected packets reaching, dropped by and delivered over the chosen paths ----
+ * No reference equivalent: the reference drops a packet with one coin flip on the Path's
+ * end-to-end reliability.  These calls spread that loss over the route: how many of the packets
+ * shd_route_loads* put on a link are expected to reach it, how many each link and each vertex
+ * drops, and how many arrive.  Entries, flags (SHD_ROUTE_DISPATCH, SHD_ROUTE_LOADS_ADD),
+ * weights (uint64_t packet counts, NULL = 1 per entry) and the failure rules are those of
+ * shd_route_loads*; the route of an entry is the one shd_route_paths reports.
+ *   Per element, all f64 and nothing contracted into a fused multiply-add: r_e = the context's
+ * reliability of edge id e (1.0f - loss, promoted), q_e = edge_packetloss[e] as given, f_v = the
+ * context's vertex factor, p_v = vertex_packetloss[v] as given; a NaN or absent vertex loss
+ * means no factor and no vertex drop.  Per source s:
+ *   F_s = 1.0*f_s, or 1.0 when f_s is absent.  pre[s] = F_s and pre[v] = pre[parent(v)] * r_e
+ *   over the parent arc: the left fold from the source, level by level, as the PROD fold.
+ *   own[t] = the u64 sum (modulo 2^64) of the weights of the source's tree-routed entries with
+ *   target t (repeated targets are summed as integers first); W_sub(v) = the u64 sum of own over
+ *   the subtree of v, the edge load shd_route_loads* give the parent arc.  Each integer is
+ *   converted to f64 once.
+ *   tree arc u -> v over edge id e, W_sub(v) != 0 : reach = (double)W_sub(v) * pre[u];
+ *            edge_reach[e] += reach; edge_drop[e] += reach * q_e.
+ *   tree target t, own[t] != 0 : arrive = (double)own[t] * pre[t]; vertex_drop[t] += arrive * p_t
+ *            where p_t is present; delivered[t] += arrive * f_t, or arrive where f_t is absent.
+ *   direct-dispatched entry (s, t, w) over the lowest edge id e joining the pair :
+ *            reach = (double)w * F_s; edge_reach[e] += reach; edge_drop[e] += reach * q_e;
+ *            arrive = reach * r_e, then the target's step above.
+ *   t == s with the lowest self-loop e : reach = (double)w * F_s; edge_reach[e] += reach;
+ *            edge_drop[e] += reach * q_e; delivered[s] += reach * r_e.  No second vertex factor:
+ *            the batch self entry's rel is (1.0*f_s)*r_ss.
+ *   the source vertex : vertex_drop[s] += (double)W_routed * p_s where p_s is present, W_routed
+ *            the u64 sum of the weights of all entries of s that did not fail (tree, direct and
+ *            self): one addend per source.
+ *   a failed entry (SHD_ROUTE_ENOEDGE, SHD_ROUTE_EUNREACH) adds its weight to *unrouted, a
+ *            uint64_t and exact (modulo 2^64), and contributes nowhere else, whatever its weight.
+ * On an undirected graph an edge has one edge_reach and one edge_drop for both directions.
+ * Nothing is subtracted anywhere and zero weights add nothing, so an element whose exact value
+ * is 0 is exactly 0.  On a graph without loss edge_reach equals edge_load of shd_route_loads*
+ * converted to double (exactly, below 2^53) and both drops are zero; with unit weights from one
+ * source delivered[t] is rel of shd_route_rows on a graph without vertex loss, and rel_lo of
+ * shd_route_ties wherever its count is 1.  The code of a failed entry comes back at the
+ * end (shd_route_loss, shd_route_pair_loss) or by the next shd_route_sync
+ * (shd_route_loss_async); a failed entry never stops the rest.
+ *   Reproducibility: the programme of one source has a fixed order and is reproducible to the
+ * bit.  The sums across sources into the outputs are f64 atomic adds in the order they arrive,
+ * the add the ECMP loads use.  A call in which no element receives more than two addends is
+ * bit-equal to the plain f64 programme (the first add onto 0.0 is exact, one more add is one
+ * commutative rounding); one source with distinct targets is such a call.  Otherwise, with R
+ * the deepest level of any source of the call and A the largest number of addends into one
+ * element, every element is within (R + 4 + A) * 2^-52 relative of the exact value
+ * (DESIGN.md 4.10).
+ *   The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the loads calls' scratch: per source of a chunk an f64 distance row, a u32 parent row
+ * and an i32 hop row, chunks sized to SHD_ROUTE_HOPS_SCRATCH (1 GiB).  One workgroup per source
+ * sorts the reached vertices by hop depth, carries pre down the levels, sums the weights up them
+ * as integers and multiplies the two in one pass; its state (22 bytes per vertex while
+ * n <= 65535, 24 above) lives in LDS up to 7,442 vertices or, on larger graphs and with
+ * SHD_ROUTE_LOSS_LDS=0, in HBM slices of 16 to 512 workgroup slots within a quarter of that
+ * budget, regrown (which synchronises the stream) when a launch needs more than the context
+ * holds.  First use blocks for what the hops calls build and for the three loss columns (per
+ * edge r_e and q_e, per vertex p_v), once per context.  On a complete graph under
+ * SHD_ROUTE_DISPATCH no rows launch and no sweep run.  Diagnostic rate: every call runs the
+ * sources' SSSP. */
+/* Device pointers, as shd_route_loads_async: d_wt[i*ld + j] = the weight of (src[i], tgt[j]),
+ * NULL = 1 per entry; d_edge_reach[n_edges], d_edge_drop[n_edges], d_vertex_drop[n_vertices],
+ * d_delivered[n_vertices] (doubles, memory of hipMalloc), d_unrouted[1]; any output may be NULL. */
+int shd_route_loss_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                         int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                         double* d_edge_reach, double* d_edge_drop, double* d_vertex_drop,
+                         double* d_delivered, uint64_t* d_unrouted, void* stream);
+/* Same with host pointers (row stride nt); blocks.  A vertex out of range is SHD_ROUTE_EINVAL
+ * for the whole call, nothing written. */
+int shd_route_loss(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                   uint32_t flags, const uint64_t* wt, double* edge_reach_out, double* edge_drop_out,
+                   double* vertex_drop_out, double* delivered_out, uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[k], pair_tgt[k], pair_wt[k]) in any order (pair_wt NULL =
+ * 1 each), grouped by source inside as shd_route_paths groups them.  Host pointers; blocks. */
+int shd_route_pair_loss(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                        const uint64_t* pair_wt, int64_t npairs, uint32_t flags, double* edge_reach_out,
+                        double* edge_drop_out, double* vertex_drop_out, double* delivered_out,
+                        uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

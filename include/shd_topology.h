@@ -178,6 +178,17 @@ int shd_topology_link_loads(shd_topology_t* top, uint64_t* edge_packets, uint64_
  * zero before the first fill; each output may be NULL. */
 int shd_topology_ecmp_link_loads(shd_topology_t* top, double* edge_packets, double* transit_packets,
                                  uint64_t* unrouted);
+/* The same pairs, counters, stored orientation and dispatch with the packets thinned out by the
+ * loss of every link and vertex on the route (shd_route_pair_loss in shd_route.h), in double:
+ * edge_reach[n_edges] = the packets expected to reach each edge id, edge_drop[n_edges] = those it
+ * drops, vertex_drop[n_vertices] = those each vertex drops as a source or a target,
+ * delivered[n_vertices] = those that arrive; *unrouted stays an exact integer.  A Path's counter
+ * holds the packets of both directions of its pair, and all of them are attributed in the
+ * stored orientation (lower attached vertex -> higher): the higher vertex's sends count as
+ * sent by the lower one, and on a directed graph over the lower -> higher route.  Same rules:
+ * engine 0, nothing cached, every total zero before the first fill; each output may be NULL. */
+int shd_topology_link_loss(shd_topology_t* top, double* edge_reach, double* edge_drop, double* vertex_drop,
+                           double* delivered, uint64_t* unrouted);
 /* ---- path folds: a per-link quantity along the stored Paths ---------------------------------
  * No reference equivalent (shd_route_pair_fold in shd_route.h).  Like the route calls above
  * these run on engine 0 under the topology lock, compute on demand (diagnostic rate), cache

@@ -29,6 +29,7 @@
 #include "path_ties.hpp"
 #include "ecmp_loads.hpp"
 #include "path_fold.hpp"
+#include "link_loss.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 #include "path_host.hpp"
@@ -158,6 +159,7 @@ struct shd_route {
     // host copies needed for lazy dense build
     std::vector<int32_t> e_src, e_dst;
     std::vector<double> e_lat, e_rel;
+    std::vector<double> e_loss, v_loss;  // the losses as given (v_loss NaN = absent): the link loss columns
     std::vector<void*> allocs;
 };
 
@@ -521,6 +523,9 @@ int shd_route_create(shd_route_t** out, const shd_graph_t* g, int device) {
     c->e_src.assign(g->edge_src, g->edge_src + m);
     c->e_dst.assign(g->edge_dst, g->edge_dst + m);
     c->e_lat.assign(g->edge_latency, g->edge_latency + m);
+    c->e_loss.assign(g->edge_packetloss, g->edge_packetloss + m);
+    c->v_loss.assign(n, NAN);
+    if (g->vertex_packetloss) c->v_loss.assign(g->vertex_packetloss, g->vertex_packetloss + n);
     HostGraph h = HostGraph::make(g);
     c->nnz = h.nnz; c->integer_w = h.integer_w; c->multigraph = h.multigraph; c->self16 = h.self16;
     c->min_w = h.min_w; c->max_w = h.max_w;

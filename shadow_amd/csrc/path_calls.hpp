@@ -1,8 +1,8 @@
 #pragma once
 // path_calls.hpp -- the path calls of the engine: hop counts and explicit routes
 // (path_hops.hpp), link loads (link_loads.hpp), path folds (path_fold.hpp), the tie envelope
-// (path_ties.hpp) and the ECMP link loads (ecmp_loads.hpp), over one set of host stages.  What needs no device is
-// path_host.hpp; here are the uploads, the launches and the entry points.  Not a stand-alone
+// (path_ties.hpp), the ECMP link loads (ecmp_loads.hpp) and the link loss (link_loss.hpp), over
+// one set of host stages.  What needs no device is path_host.hpp; here are the uploads, the launches and the entry points.  Not a stand-alone
 // header: engine.hip includes it once struct shd_route, hip_check, upload, DevBuf and
 // shd_route_rows_async are defined.
 
@@ -155,7 +155,7 @@ DevTies dev_ties(const shd_route* c) {
 
 // the buffers grown on demand (shd_route_destroy; the uploads are in the context's allocs)
 void path_free(PathDev& p) {
-    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.buf})
+    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.lo_ws.p, p.buf})
         if (q) (void)hipFree(q);
 }
 
@@ -1000,6 +1000,207 @@ int shd_route_pair_ecmp_loads(shd_route_t* c, const int32_t* pair_src, const int
     if ((rc = out.add_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, (const long long*)doff.p,
                               pair_wt ? dw.p : nullptr, flags)) ||
         (rc = sc.sync(c)) || (rc = out.finish(flags, edge_load_out, transit_out, unrouted_out)))
+        return rc;
+    return sc.soft;
+}
+
+}  // extern "C"
+
+// ---- link loss ----
+namespace {
+
+// the per-element columns, once per context: 1.0f - loss and the loss as given of every edge
+// id, the loss as given of every vertex (NaN = absent); the vertex factors are the context's
+int ensure_loss(shd_route* c) {
+    PathDev& p = c->path;
+    if (p.lo_ready) return SHD_ROUTE_OK;
+    int rc = ensure_hops(c);
+    if (!rc) rc = upload(c, &p.lo_r, c->e_rel);
+    if (!rc) rc = upload(c, &p.lo_q, c->e_loss);
+    if (!rc) rc = upload(c, &p.lo_p, c->v_loss);
+    if (!rc && loss_fits_lds(c->n))
+        rc = hip_check(hipFuncSetAttribute((const void*)loss_tree_kernel<uint16_t, true, 1024>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLossLdsBudget));
+    if (rc) return rc;
+    p.lo_ready = 1;
+    return SHD_ROUTE_OK;
+}
+
+// the sweeps of k sources and their entries (loss_tree_kernel); HBM slices as the loads', regrown as theirs
+int lo_tree(shd_route* c, const uint32_t* par, const int32_t* hrow, const int32_t* d_src, int k, const int32_t* d_tgt,
+            int nt, long long ld, const long long* d_eoff, const uint64_t* d_wt, int mode, const LossOuts& o,
+            hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    const DevLoss q{c->path.lo_r, c->path.lo_q, c->d_vf, c->path.lo_p};
+    const char* e = getenv("SHD_ROUTE_LOSS_LDS");  // "0": the HBM form on graphs the LDS form takes
+    const StateLaunch f = state_form(n, mode, k, kLoSmall, LossLayout<uint16_t>::make(n).total, kLossLdsBudget,
+                                     knob_off(e), a16(LossLayout<uint16_t>::make(n).total),
+                                     a16(LossLayout<uint32_t>::make(n).total), hp_budget() / 4);
+    return launch_state(c->path.lo_ws, f, st, [&](auto tag, char* ws, size_t stride) {
+        using F = decltype(tag);
+        hipLaunchKernelGGL((loss_tree_kernel<typename F::t, F::lds, 1024>), dim3(f.grid), dim3(1024), f.lds, st, g, q,
+                           par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, (const unsigned long long*)d_wt, mode, o, ws,
+                           stride, c->d_err);
+    });
+}
+
+// The loss of ns sources added into the outputs; entries as ld_sources takes them.
+int lo_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
+               const long long* d_eoff, const uint64_t* d_wt, uint32_t flags, const LossOuts& o, hipStream_t st) {
+    int rc = ensure_loss(c);
+    if (rc) return rc;
+    const int mode = hp_mode(c, flags);
+    return source_chunks(c, ns, mode, true, [&](int i0, int k, double* dist, uint32_t* par, int32_t* hrow) {
+        if (par && (rc = hp_trees(c, d_src + i0, k, dist, par, hrow, st))) return rc;
+        return lo_tree(c, par, hrow, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr,
+                       d_wt && !d_eoff ? d_wt + (long long)i0 * ld : d_wt, mode, o, st);
+    });
+}
+
+// zero the outputs a call without SHD_ROUTE_LOADS_ADD starts from (0.0 is all bits zero)
+int lo_zero(shd_route* c, uint32_t flags, const LossOuts& o, hipStream_t st) {
+    if (flags & SHD_ROUTE_LOADS_ADD) return SHD_ROUTE_OK;
+    const size_t m8 = sizeof(double) * (size_t)c->m, n8 = sizeof(double) * (size_t)c->n;
+    if ((o.edge_reach && m8 && hipMemsetAsync(o.edge_reach, 0, m8, st) != hipSuccess) ||
+        (o.edge_drop && m8 && hipMemsetAsync(o.edge_drop, 0, m8, st) != hipSuccess) ||
+        (o.vertex_drop && hipMemsetAsync(o.vertex_drop, 0, n8, st) != hipSuccess) ||
+        (o.delivered && hipMemsetAsync(o.delivered, 0, n8, st) != hipSuccess) ||
+        (o.unrouted && hipMemsetAsync(o.unrouted, 0, sizeof(uint64_t), st) != hipSuccess))
+        return SHD_ROUTE_EDEVICE;
+    return SHD_ROUTE_OK;
+}
+
+// the caller's host outputs of a blocking call
+struct LossHost {
+    double* edge_reach; double* edge_drop; double* vertex_drop; double* delivered;
+    uint64_t* unrouted;
+};
+
+// device accumulators of the blocking calls, as LoadsOut: four columns in double, unrouted in u64
+struct LossOut {
+    DevBuf de, dd, dv, dl, du;
+    int m = 0, n = 0;
+    int init(const shd_route* c) {
+        m = c->m; n = c->n;
+        const size_t m8 = sizeof(double) * (size_t)m, n8 = sizeof(double) * (size_t)n;
+        int rc;
+        if ((rc = de.alloc(m8)) || (rc = dd.alloc(m8)) || (rc = dv.alloc(n8)) || (rc = dl.alloc(n8)) ||
+            (rc = du.alloc(sizeof(uint64_t))))
+            return rc;
+        if ((m && (hipMemset(de.p, 0, m8) != hipSuccess || hipMemset(dd.p, 0, m8) != hipSuccess)) ||
+            hipMemset(dv.p, 0, n8) != hipSuccess || hipMemset(dl.p, 0, n8) != hipSuccess ||
+            hipMemset(du.p, 0, sizeof(uint64_t)) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        return SHD_ROUTE_OK;
+    }
+    LossOuts outs() const {
+        return LossOuts{(double*)de.p, (double*)dd.p, (double*)dv.p, (double*)dl.p, (unsigned long long*)du.p};
+    }
+    int finish(uint32_t flags, const LossHost& h) {
+        const bool add = (flags & SHD_ROUTE_LOADS_ADD) != 0;
+        int rc;
+        if ((rc = EcmpOut::take(h.edge_reach, de.p, (size_t)m, add)) ||
+            (rc = EcmpOut::take(h.edge_drop, dd.p, (size_t)m, add)) ||
+            (rc = EcmpOut::take(h.vertex_drop, dv.p, (size_t)n, add)) ||
+            (rc = EcmpOut::take(h.delivered, dl.p, (size_t)n, add)))
+            return rc;
+        return EcmpOut::take(h.unrouted, du.p, 1, add);
+    }
+    // ns sources on the null stream into the accumulators
+    int add_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, const long long* d_eoff,
+                    const void* d_wt, uint32_t flags) {
+        return lo_sources(c, d_src, ns, d_tgt, nt, nt, d_eoff, (const uint64_t*)d_wt, flags, outs(), nullptr);
+    }
+};
+
+// the outputs of a blocking call that has nothing to route
+void lo_host_zero(const shd_route* c, uint32_t flags, const LossHost& h) {
+    if (flags & SHD_ROUTE_LOADS_ADD) return;
+    if (h.edge_reach) std::fill(h.edge_reach, h.edge_reach + c->m, 0.0);
+    if (h.edge_drop) std::fill(h.edge_drop, h.edge_drop + c->m, 0.0);
+    if (h.vertex_drop) std::fill(h.vertex_drop, h.vertex_drop + c->n, 0.0);
+    if (h.delivered) std::fill(h.delivered, h.delivered + c->n, 0.0);
+    if (h.unrouted) *h.unrouted = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_loss_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                         int64_t ld, uint32_t flags, const uint64_t* d_wt, double* d_edge_reach, double* d_edge_drop,
+                         double* d_vertex_drop, double* d_delivered, uint64_t* d_unrouted, void* stream) {
+    if (!block_args_ok(c, d_src, ns, d_tgt, nt, ld)) return SHD_ROUTE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const LossOuts o{d_edge_reach, d_edge_drop, d_vertex_drop, d_delivered, (unsigned long long*)d_unrouted};
+    int rc = lo_zero(c, flags, o, st);
+    if (rc || ns == 0 || nt == 0) return rc;
+    return lo_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, d_wt, flags, o, st);
+}
+
+int shd_route_loss(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
+                   const uint64_t* wt, double* edge_reach_out, double* edge_drop_out, double* vertex_drop_out,
+                   double* delivered_out, uint64_t* unrouted_out) {
+    if (!block_args_ok(c, src, ns, tgt, nt, nt)) return SHD_ROUTE_EINVAL;
+    for (int32_t i = 0; i < ns; i++)
+        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
+    for (int32_t j = 0; j < nt; j++)
+        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
+    const LossHost h{edge_reach_out, edge_drop_out, vertex_drop_out, delivered_out, unrouted_out};
+    if (ns == 0 || nt == 0) {
+        lo_host_zero(c, flags, h);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)nt;
+    const int32_t chunk = host_chunk(ns, row_bytes);
+    DevBuf dw;
+    LossOut out;
+    int rc;
+    if ((wt && (rc = dw.alloc(row_bytes * chunk))) || (rc = out.init(c))) return rc;
+    return host_blocks(
+        c, src, ns, tgt, nt, chunk,
+        [&](int32_t i0, int32_t k, const int32_t* d_src, const int32_t* d_tgt) {
+            if (wt && hipMemcpy(dw.p, wt + (size_t)i0 * nt, row_bytes * k, hipMemcpyHostToDevice) != hipSuccess)
+                return SHD_ROUTE_EDEVICE;
+            return out.add_sources(c, d_src, k, d_tgt, nt, nullptr, wt ? dw.p : nullptr, flags);
+        },
+        [&](int32_t i0, int32_t k) { return i0 + k < ns ? SHD_ROUTE_OK : out.finish(flags, h); });
+}
+
+int shd_route_pair_loss(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, const uint64_t* pair_wt,
+                        int64_t npairs, uint32_t flags, double* edge_reach_out, double* edge_drop_out,
+                        double* vertex_drop_out, double* delivered_out, uint64_t* unrouted_out) {
+    if (!pair_args_ok(c, pair_src, pair_tgt, npairs) || !pairs_in_range(c, pair_src, pair_tgt, (int)npairs))
+        return SHD_ROUTE_EINVAL;
+    const int np = (int)npairs;
+    const LossHost h{edge_reach_out, edge_drop_out, vertex_drop_out, delivered_out, unrouted_out};
+    if (np == 0) {
+        lo_host_zero(c, flags, h);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // the entries of distinct source u are the grouped positions first[u] .. first[u + 1]
+    const PairGroups pg = group_pairs(pair_src, pair_tgt, pair_wt, np);
+    const int nu = (int)pg.us.size();
+    DevBuf dsrc, dtgt, dw, doff;
+    LossOut out;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
+        (pair_wt && (rc = dw.alloc(sizeof(uint64_t) * (size_t)np))) ||
+        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) || (rc = out.init(c)))
+        return rc;
+    if (hipMemcpy(dsrc.p, pg.us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, pg.gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
+        (pair_wt && hipMemcpy(dw.p, pg.gw.data(), sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(doff.p, pg.first.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess)
+        return SHD_ROUTE_EDEVICE;
+    SoftCode sc;
+    if ((rc = out.add_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, (const long long*)doff.p,
+                              pair_wt ? dw.p : nullptr, flags)) ||
+        (rc = sc.sync(c)) || (rc = out.finish(flags, h)))
         return rc;
     return sc.soft;
 }

@@ -97,8 +97,8 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 }
 
 // ---- the form of a per-source state kernel ----
-// hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, ties_dag_kernel and ecmp_dag_kernel keep one source's
-// state per workgroup:
+// hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, loss_tree_kernel, ties_dag_kernel and
+// ecmp_dag_kernel keep one source's state per workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
 // else u16 (n <= 65535) or u32 state in HBM slices, one per resident workgroup.
@@ -157,6 +157,11 @@ struct PathDev {
     size_t buf_cap = 0;
     PathSlices fo_ws;  // folds: the HBM slices, and
     int fo_ready = 0;  // the LDS form's dynamic-LDS limit is raised
+    // link loss: per edge id 1.0f - loss and the loss as given, per vertex the loss as given
+    // (NaN = absent), built at the first loss call; and the HBM slices
+    int lo_ready = 0;
+    double* lo_r = nullptr; double* lo_q = nullptr; double* lo_p = nullptr;
+    PathSlices lo_ws;
 };
 
 }  // namespace shd

@@ -830,6 +830,35 @@ int shd_topology_ecmp_link_loads(shd_topology_t* t, double* edge_packets, double
     return rc;
 }
 
+/* the same pairs and counters thinned out by the loss of every link and vertex on the way
+ * (shd_route_pair_loss on engine 0, nothing cached) */
+int shd_topology_link_loss(shd_topology_t* t, double* edge_reach, double* edge_drop, double* vertex_drop,
+                           double* delivered, uint64_t* unrouted) {
+    if (!t) return SHD_ROUTE_EINVAL;
+    for (int32_t e = 0; e < t->g.n_edges; e++) {
+        if (edge_reach) edge_reach[e] = 0.0;
+        if (edge_drop) edge_drop[e] = 0.0;
+    }
+    for (int32_t v = 0; v < t->n; v++) {
+        if (vertex_drop) vertex_drop[v] = 0.0;
+        if (delivered) delivered[v] = 0.0;
+    }
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0;
+    int rc = counted_pairs(t, &ps, &pt, &pw, &np);
+    if (!rc && np) {
+        rc = shd_route_pair_loss(t->eng[0], ps, pt, pw, (int64_t)np, SHD_ROUTE_DISPATCH, edge_reach, edge_drop,
+                                 vertex_drop, delivered, unrouted);
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;  /* as above */
+    }
+    pthread_mutex_unlock(&t->lock);
+    free(ps); free(pt); free(pw);
+    return rc;
+}
+
 /* ---- path folds along the stored Paths (shd_route_pair_fold on engine 0, nothing cached) ---- */
 
 int shd_topology_edge_jitter(shd_topology_t* t, double* out) {

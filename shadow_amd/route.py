@@ -90,6 +90,7 @@ EXPORTS = (
     "shd_route_ties_async", "shd_route_ties",
     "shd_route_ecmp_loads_async", "shd_route_ecmp_loads", "shd_route_pair_ecmp_loads",
     "shd_route_fold_async", "shd_route_fold", "shd_route_pair_fold",
+    "shd_route_loss_async", "shd_route_loss", "shd_route_pair_loss",
 )
 
 _lib = None
@@ -184,6 +185,12 @@ def load_library():
     L.shd_route_ecmp_loads.argtypes = [P, P, I32, P, I32, U32, P, P, P, P]
     L.shd_route_pair_ecmp_loads.restype = C.c_int
     L.shd_route_pair_ecmp_loads.argtypes = [P, P, P, P, I64, U32, P, P, P]
+    L.shd_route_loss_async.restype = C.c_int
+    L.shd_route_loss_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P, P, P, P]
+    L.shd_route_loss.restype = C.c_int
+    L.shd_route_loss.argtypes = [P, P, I32, P, I32, U32, P, P, P, P, P, P]
+    L.shd_route_pair_loss.restype = C.c_int
+    L.shd_route_pair_loss.argtypes = [P, P, P, P, I64, U32, P, P, P, P, P]
     L.shd_route_fold_async.restype = C.c_int
     L.shd_route_fold_async.argtypes = [P, P, I32, P, I32, I64, U32, P, I32, P, P, I64, P]
     L.shd_route_fold.restype = C.c_int
@@ -445,6 +452,58 @@ class RouteEngine:
         _check(rc, "shd_route_pair_ecmp_loads")
         return el, tr, int(un[0])
 
+    def _loss_out(self, out):
+        if out is not None:
+            return out
+        m, n = self.info["n_edges"], self.info["n_vertices"]
+        return (np.zeros(m, np.float64), np.zeros(m, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64),
+                np.zeros(1, np.uint64))
+
+    def loss(self, sources, targets, weights=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_loss: (edge_reach, edge_drop, vertex_drop, delivered, unrouted) of the (source,
+        target) block: the expected packets that reach each edge id, that each edge and each
+        vertex drops and that arrive at each vertex (float64), and the summed weight of the
+        failed entries (an exact integer).  weights as loads().  out: the five arrays of an
+        earlier call (unrouted as a 1-element uint64 array), any of them None for an output not
+        wanted; add=True (SHD_ROUTE_LOADS_ADD) adds into them.  A missing self-loop or an
+        unreachable target raises RouteError; ``err.partial`` then holds the results."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        er, ed, vd, dl, un = self._loss_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_loss(self._h, _p(s), len(s), _p(t), len(t), flags, _p(w), _p(er), _p(ed), _p(vd),
+                                           _p(dl), _p(un))
+        res = (er, ed, vd, dl, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_loss")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_loss")
+        return res
+
+    def pair_loss(self, pair_src, pair_tgt, pair_wt=None, dispatch: bool = True, out=None, add: bool = False):
+        """shd_route_pair_loss: as loss() for a list of (source, target, weight) pairs in any
+        order, repeats adding up (pair_wt None = 1 each)."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        er, ed, vd, dl, un = self._loss_out(out)
+        flags = (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0)
+        rc = load_library().shd_route_pair_loss(self._h, _p(s), _p(t), _p(w), len(s), flags, _p(er), _p(ed), _p(vd),
+                                                _p(dl), _p(un))
+        res = (er, ed, vd, dl, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_loss")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_pair_loss")
+        return res
+
     def _fold_args(self, ops, values):
         o = np.ascontiguousarray(ops, np.int32).reshape(-1)
         v = np.ascontiguousarray(values, np.float64)
@@ -505,6 +564,21 @@ class RouteEngine:
             self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0, _p(o), len(o), ptr(d_val),
             ptr(d_out), plane, C.c_void_p(stream) if stream else None)
         _check(rc, "shd_route_fold_async")
+
+    def loss_async(self, d_src, d_tgt, d_wt, d_edge_reach, d_edge_drop, d_vertex_drop, d_delivered, d_unrouted,
+                   stream=None, dispatch=True, ld=None, add=False):
+        """shd_route_loss_async over device tensors: int32 sources and targets, 64-bit integer
+        weights (None = 1 per entry), float64 edge_reach and edge_drop (n_edges elements),
+        vertex_drop and delivered (n_vertices) and a 64-bit integer unrouted (1 element); any
+        output may be None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_loss_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, (DISPATCH if dispatch else 0) | (LOADS_ADD if add else 0),
+            ptr(d_wt), ptr(d_edge_reach), ptr(d_edge_drop), ptr(d_vertex_drop), ptr(d_delivered), ptr(d_unrouted),
+            C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_loss_async")
 
     def ecmp_loads_async(self, d_src, d_tgt, d_wt, d_edge_load, d_transit, d_unrouted, stream=None, dispatch=True,
                          ld=None, add=False):

@@ -31,7 +31,7 @@ EXPORTS = (
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
     "shd_topology_link_loads", "shd_topology_ecmp_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
-    "shd_topology_edge_jitter", "shd_topology_fold_pairs",
+    "shd_topology_edge_jitter", "shd_topology_fold_pairs", "shd_topology_link_loss",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
@@ -116,6 +116,8 @@ def load_library():
     L.shd_topology_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_ecmp_link_loads.restype = C.c_int
     L.shd_topology_ecmp_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_link_loss.restype = C.c_int
+    L.shd_topology_link_loss.argtypes = [P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_edge_jitter.restype = C.c_int
     L.shd_topology_edge_jitter.argtypes = [P, P]
     L.shd_topology_fold_pairs.restype = C.c_int
@@ -404,6 +406,21 @@ class Topology:
         if rc:
             raise RuntimeError(f"ecmp_link_loads failed ({rc})")
         return ep, tp, int(un.value)
+
+    def link_loss(self):
+        """shd_topology_link_loss: (edge_reach, edge_drop, vertex_drop, delivered, unrouted) of the
+        cached Paths' packet counters, thinned out by the loss of every link and vertex on the
+        route: float64 totals per edge id and per vertex, an exact integer unrouted.  A counter
+        holds both directions of its pair; all of it is attributed in the stored orientation."""
+        L = load_library()
+        m, n = int(L.shd_topology_edge_count(self._h)), int(L.shd_topology_vertex_count(self._h))
+        er, ed = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        vd, dl = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        un = C.c_uint64()
+        rc = L.shd_topology_link_loss(self._h, *(C.c_void_p(a.ctypes.data) for a in (er, ed, vd, dl)), C.byref(un))
+        if rc:
+            raise RuntimeError(f"link_loss failed ({rc})")
+        return er, ed, vd, dl, int(un.value)
 
     def edge_jitter(self):
         """shd_topology_edge_jitter: the graphml's jitter edge attribute per edge id (NaN where
