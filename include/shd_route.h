@@ -14,8 +14,9 @@
  * shd_route_paths) and the link loads calls (shd_route_loads*, shd_route_pair_loads) run a
  * rows launch inside and fall under the same rule, and so do the tie envelope calls
  * (shd_route_ties*), the ECMP link loads calls (shd_route_ecmp_loads*,
- * shd_route_pair_ecmp_loads), the path fold calls (shd_route_fold*, shd_route_pair_fold) and
- * the link loss calls (shd_route_loss*, shd_route_pair_loss).
+ * shd_route_pair_ecmp_loads), the path fold calls (shd_route_fold*, shd_route_pair_fold),
+ * the link loss calls (shd_route_loss*, shd_route_pair_loss) and the link outage calls
+ * (shd_route_outage*, shd_route_pair_outage).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -40,15 +41,16 @@
  *                  the hops, loads, folds, ties and ECMP loads calls (their in-CSR with edge ids; the
  *                  ties and ECMP loads calls also their per-arc reliabilities and out-CSR, the
  *                  ECMP loads calls the out-arcs' edge ids; the loss calls also their per-edge
- *                  and per-vertex loss columns); all once per context
+ *                  and per-vertex loss columns, the outage calls the edges' ends and latencies
+ *                  and the self-loop lists); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
  *                  the hops, loads, folds, ties and ECMP loads calls when their source chunk
- *                  grows (the loss calls follow the loads calls), shd_route_loads_async,
- *                  shd_route_fold_async, shd_route_ties_async, shd_route_ecmp_loads_async and
- *                  shd_route_loss_async in their HBM forms when the slices grow (those
- *                  synchronise the stream)
+ *                  grows (the loss and outage calls follow the loads calls),
+ *                  shd_route_loads_async, shd_route_fold_async, shd_route_ties_async,
+ *                  shd_route_ecmp_loads_async, shd_route_loss_async and shd_route_outage_async
+ *                  in their HBM forms when the slices grow (those synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -539,6 +541,74 @@ int shd_route_pair_loss(shd_route_t* ctx, const int32_t* pair_src, const int32_t
                         const uint64_t* pair_wt, int64_t npairs, uint32_t flags, double* edge_reach_out,
                         double* edge_drop_out, double* vertex_drop_out, double* delivered_out,
                         uint64_t* unrouted_out);
+
+/* ---- link outages: what the entries lose when a set of edges goes down ----
+ * No reference equivalent: Shadow 1.14 has no outage model, a user loads another topology.
+ * Scenario k is the set F_k = scn_edge[scn_off[k] .. scn_off[k+1]) of edge ids, duplicates
+ * allowed; G_k is the context's graph without those edges, the others in their order (an
+ * undirected edge loses both arcs, a directed edge its one arc).  A vertex outage is the
+ * scenario of the vertex's incident edges.  Every entry (src[i], tgt[j], weight) is judged
+ * without dispatch -- tree routes and the batch self entry, as shd_route_rows gives them with
+ * flags 0 -- so flags must be 0: SHD_ROUTE_DISPATCH or any other bit is SHD_ROUTE_EINVAL.
+ *   old = the entry in G.  An entry that fails in G (SHD_ROUTE_ENOEDGE, SHD_ROUTE_EUNREACH)
+ * fails as in the loads calls: its code is raised, its weight goes to *unrouted once (not once
+ * per scenario) and it takes part in no scenario.
+ *   new = the entry of a context created from G_k: for t != s the shortest latency in G_k (the
+ * f64 left fold from the source), for t == s the latency of the lowest self-loop of s not in F_k.
+ *   Per scenario, stats[k*SHD_ROUTE_OUTAGE_NSTAT + ...] in u64 adds, exact mod 2^64 and
+ * independent of order:
+ *     SHD_ROUTE_OUTAGE_HIT     the weight of the entries whose old route, the one shd_route_paths
+ *                              reports, uses an edge of F_k (for a self entry: the self-loop);
+ *     SHD_ROUTE_OUTAGE_CUT     the weight of the entries without a route in G_k;
+ *     SHD_ROUTE_OUTAGE_SLOWER  the weight of the entries routable in both with new > old;
+ * max_add[k] = the largest new - old (one f64 subtraction per entry) over the slower entries,
+ * 0.0 without any (an entry of weight 0 is an entry too): an exact maximum, independent of
+ * order.  lat[(k*ns + i)*ld + j], if asked
+ * for, is the new latency, NaN where cut or where the entry failed in G; it is bit-equal to
+ * lat of shd_route_rows with flags 0 on a context created from G_k.  An entry that is hit but
+ * has a tied alternative keeps its latency and counts in hit only.  Reliability and hops of the
+ * new routes are not computed: create a context for the one scenario wanted in full.
+ *   nscn == 0 writes only *unrouted; an empty scenario gives zeros and the old latencies.
+ *   The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the loads calls' scratch: distance, parent and hop rows per source of a chunk, chunks
+ * sized to SHD_ROUTE_HOPS_SCRATCH.  A work unit is one source with a slab of up to 1,024
+ * scenarios, the grid covers the units.  A unit sorts the source's tree by hop depth, finds
+ * the scenarios that fail a parent arc (or the source's lowest self-loop) and repairs each of
+ * them in the marked subtrees alone: seed from the unmarked in-neighbours, then pull sweeps
+ * until nothing changes.  The state (17 bytes per vertex while n <= 65535, 21
+ * above) lives in LDS up to 9,328 vertices or, on larger graphs and with
+ * SHD_ROUTE_OUTAGE_LDS=0, in HBM slices of 16 to 512 workgroup slots within a quarter of
+ * that budget, regrown (which synchronises the stream) when a launch needs more.  First use
+ * blocks for what the hops calls build and for the edge ends, latencies and self-loop lists,
+ * once per context.  Diagnostic rate: every call runs the sources' SSSP. */
+#define SHD_ROUTE_OUTAGE_HIT 0
+#define SHD_ROUTE_OUTAGE_CUT 1
+#define SHD_ROUTE_OUTAGE_SLOWER 2
+#define SHD_ROUTE_OUTAGE_NSTAT 3
+/* Device pointers, as shd_route_loads_async: d_wt[i*ld + j], NULL = 1 per entry;
+ * d_scn_off[nscn + 1] (from 0, rising), d_scn_edge each scenario ascending; d_stats
+ * [nscn * SHD_ROUTE_OUTAGE_NSTAT], d_max_add[nscn], d_lat[((int64)k*ns + i)*ld + j],
+ * d_unrouted[1]; any output may be NULL.  A validation kernel raises SHD_ROUTE_EINVAL on the
+ * error word for an offset, range or order violation (the outputs are then undefined); the
+ * main kernel indexes no memory with an unchecked id. */
+int shd_route_outage_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                           int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                           const int64_t* d_scn_off, const int32_t* d_scn_edge, int32_t nscn,
+                           uint64_t* d_stats, double* d_max_add, double* d_lat, uint64_t* d_unrouted,
+                           void* stream);
+/* Same with host pointers (row stride nt); blocks.  Scenario ids in any order: each scenario is
+ * sorted inside.  An id outside [0, n_edges) or a vertex out of range is SHD_ROUTE_EINVAL for
+ * the whole call, nothing written. */
+int shd_route_outage(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                     uint32_t flags, const uint64_t* wt, const int64_t* scn_off, const int32_t* scn_edge,
+                     int32_t nscn, uint64_t* stats_out, double* max_add_out, double* lat_out,
+                     uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[p], pair_tgt[p], pair_wt[p]) in any order (pair_wt NULL =
+ * 1 each); lat_out[k*npairs + p] in the caller's pair order.  Host pointers; blocks. */
+int shd_route_pair_outage(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                          const uint64_t* pair_wt, int64_t npairs, uint32_t flags, const int64_t* scn_off,
+                          const int32_t* scn_edge, int32_t nscn, uint64_t* stats_out, double* max_add_out,
+                          double* lat_out, uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

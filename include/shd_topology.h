@@ -189,6 +189,17 @@ int shd_topology_ecmp_link_loads(shd_topology_t* top, double* edge_packets, doub
  * engine 0, nothing cached, every total zero before the first fill; each output may be NULL. */
 int shd_topology_link_loss(shd_topology_t* top, double* edge_reach, double* edge_drop, double* vertex_drop,
                            double* delivered, uint64_t* unrouted);
+/* What the same pairs and counters (stored orientation, the counter as the weight) lose when
+ * links go down: scenario k fails the edge ids scn_edge[scn_off[k] .. scn_off[k+1]), in any
+ * order (shd_route_pair_outage in shd_route.h).  stats[nscn * SHD_ROUTE_OUTAGE_NSTAT] = per
+ * scenario the packets whose route used a failed link, those cut off and those that get
+ * slower; max_add[nscn] = the largest added latency; *unrouted = the packets of pairs without a
+ * route in the whole graph.  The outage calls judge tree routes only: a topology whose cache
+ * dispatches (a complete graph, or prefer-direct) returns SHD_ROUTE_EUNSUPPORTED.  An id outside
+ * [0, n_edges) is SHD_ROUTE_EINVAL, nothing written.  Same rules: engine 0 under the lock,
+ * nothing cached, every total zero before the first fill; each output may be NULL. */
+int shd_topology_link_outage(shd_topology_t* top, const int64_t* scn_off, const int32_t* scn_edge, int32_t nscn,
+                             uint64_t* stats, double* max_add, uint64_t* unrouted);
 /* ---- path folds: a per-link quantity along the stored Paths ---------------------------------
  * No reference equivalent (shd_route_pair_fold in shd_route.h).  Like the route calls above
  * these run on engine 0 under the topology lock, compute on demand (diagnostic rate), cache

@@ -30,6 +30,7 @@
 #include "ecmp_loads.hpp"
 #include "path_fold.hpp"
 #include "link_loss.hpp"
+#include "link_outage.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 #include "path_host.hpp"

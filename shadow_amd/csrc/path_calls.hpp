@@ -1,7 +1,7 @@
 #pragma once
 // path_calls.hpp -- the path calls of the engine: hop counts and explicit routes
 // (path_hops.hpp), link loads (link_loads.hpp), path folds (path_fold.hpp), the tie envelope
-// (path_ties.hpp), the ECMP link loads (ecmp_loads.hpp) and the link loss (link_loss.hpp), over
+// (path_ties.hpp), the ECMP link loads (ecmp_loads.hpp), the link loss (link_loss.hpp) and the link outages (link_outage.hpp), over
 // one set of host stages.  What needs no device is path_host.hpp; here are the uploads, the launches and the entry points.  Not a stand-alone
 // header: engine.hip includes it once struct shd_route, hip_check, upload, DevBuf and
 // shd_route_rows_async are defined.
@@ -155,7 +155,7 @@ DevTies dev_ties(const shd_route* c) {
 
 // the buffers grown on demand (shd_route_destroy; the uploads are in the context's allocs)
 void path_free(PathDev& p) {
-    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.lo_ws.p, p.buf})
+    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.lo_ws.p, p.ou_ws.p, p.buf})
         if (q) (void)hipFree(q);
 }
 
@@ -1202,6 +1202,289 @@ int shd_route_pair_loss(shd_route_t* c, const int32_t* pair_src, const int32_t* 
                               pair_wt ? dw.p : nullptr, flags)) ||
         (rc = sc.sync(c)) || (rc = out.finish(flags, h)))
         return rc;
+    return sc.soft;
+}
+
+}  // extern "C"
+
+// ---- link outages ----
+namespace {
+
+// the per-element columns, once per context: the ends and the latency of every edge id and
+// each vertex's self-loop edge ids, ascending
+int ensure_outage(shd_route* c) {
+    PathDev& p = c->path;
+    if (p.ou_ready) return SHD_ROUTE_OK;
+    const int n = c->n;
+    std::vector<int> srow(n + 1, 0), seid;
+    for (int e = 0; e < c->m; e++)
+        if (c->e_src[e] == c->e_dst[e]) srow[c->e_src[e] + 1]++;
+    for (int v = 0; v < n; v++) srow[v + 1] += srow[v];
+    seid.resize(srow[n]);
+    std::vector<int> fill(srow.begin(), srow.end() - 1);
+    for (int e = 0; e < c->m; e++)
+        if (c->e_src[e] == c->e_dst[e]) seid[fill[c->e_src[e]]++] = e;
+    int rc = ensure_hops(c);
+    if (!rc) rc = upload(c, &p.ou_ea, c->e_src);
+    if (!rc) rc = upload(c, &p.ou_eb, c->e_dst);
+    if (!rc) rc = upload(c, &p.ou_lat, c->e_lat);
+    if (!rc) rc = upload(c, &p.ou_srow, srow);
+    if (!rc) rc = upload(c, &p.ou_seid, seid);
+    if (!rc && outage_fits_lds(n))
+        rc = hip_check(hipFuncSetAttribute((const void*)outage_repair_kernel<uint16_t, true, 1024>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOutageLdsBudget));
+    if (rc) return rc;
+    p.ou_ready = 1;
+    return SHD_ROUTE_OK;
+}
+
+struct OutageScn {  // the scenarios of a call on the device
+    const int64_t* off;
+    const int32_t* edge;
+    int nscn;
+};
+
+DevOutage dev_outage(const shd_route* c, const OutageScn& s) {
+    const PathDev& p = c->path;
+    DevOutage q;
+    q.m = c->m; q.directed = c->directed;
+    q.ea = p.ou_ea; q.eb = p.ou_eb; q.lat = p.ou_lat; q.srow = p.ou_srow; q.seid = p.ou_seid;
+    q.off = (const long long*)s.off; q.edge = s.edge; q.nscn = s.nscn;
+    return q;
+}
+
+// the repairs of k sources and their entries over every scenario (outage_repair_kernel); the
+// grid covers the units, HBM slices as the loads', regrown as theirs
+int ou_repair(shd_route* c, const double* dist, const uint32_t* par, const int32_t* hrow, const int32_t* d_src, int k,
+              const int32_t* d_tgt, int nt, long long ld, const long long* d_eoff, const uint64_t* d_wt,
+              const OutageScn& scn, const OutageOuts& o, hipStream_t st) {
+    const int n = c->n;
+    const DevHops g = dev_hops(c);
+    const DevOutage q = dev_outage(c, scn);
+    const OutageUnits U = OutageUnits::make(k, scn.nscn);
+    const char* e = getenv("SHD_ROUTE_OUTAGE_LDS");  // "0": the HBM form on graphs the LDS form takes
+    const StateLaunch f = state_form(n, 0, (int)std::min<long long>(U.units, 0x7FFFFFFF), kOuSmall,
+                                     OutageLayout<uint16_t>::make(n).total, kOutageLdsBudget, knob_off(e),
+                                     a16(OutageLayout<uint16_t>::make(n).total),
+                                     a16(OutageLayout<uint32_t>::make(n).total), hp_budget() / 4);
+    return launch_state(c->path.ou_ws, f, st, [&](auto tag, char* ws, size_t stride) {
+        using F = decltype(tag);
+        hipLaunchKernelGGL((outage_repair_kernel<typename F::t, F::lds, 1024>), dim3(f.grid), dim3(1024), f.lds, st, g, q,
+                           U, dist, par, hrow, d_src, k, d_tgt, nt, ld, d_eoff, (const unsigned long long*)d_wt, o, ws,
+                           stride, c->d_err);
+    });
+}
+
+// The outages of ns sources added into the outputs; entries as ld_sources takes them.  The
+// block's chunk i0 writes from row i0 of every plane of o.lat on.
+int ou_sources(shd_route* c, const int32_t* d_src, int ns, const int32_t* d_tgt, int nt, long long ld,
+               const long long* d_eoff, const uint64_t* d_wt, const OutageScn& scn, const OutageOuts& o,
+               hipStream_t st) {
+    int rc = ensure_outage(c);
+    if (rc) return rc;
+    return source_chunks(c, ns, 0, true, [&](int i0, int k, double* dist, uint32_t* par, int32_t* hrow) {
+        if ((rc = hp_trees(c, d_src + i0, k, dist, par, hrow, st))) return rc;
+        OutageOuts oc = o;
+        if (oc.lat && !d_eoff) oc.lat += (long long)i0 * ld;
+        return ou_repair(c, dist, par, hrow, d_src + i0, k, d_tgt, nt, ld, d_eoff ? d_eoff + i0 : nullptr,
+                         d_wt && !d_eoff ? d_wt + (long long)i0 * ld : d_wt, scn, oc, st);
+    });
+}
+
+// zero the statistics a call starts from (0.0 is all bits zero)
+int ou_zero(const OutageOuts& o, int nscn, hipStream_t st) {
+    const size_t sb = sizeof(uint64_t) * SHD_ROUTE_OUTAGE_NSTAT * (size_t)nscn;
+    if ((o.stats && sb && hipMemsetAsync(o.stats, 0, sb, st) != hipSuccess) ||
+        (o.max_add && nscn && hipMemsetAsync(o.max_add, 0, sizeof(double) * (size_t)nscn, st) != hipSuccess) ||
+        (o.unrouted && hipMemsetAsync(o.unrouted, 0, sizeof(uint64_t), st) != hipSuccess))
+        return SHD_ROUTE_EDEVICE;
+    return SHD_ROUTE_OK;
+}
+
+// The scenarios of a blocking call: each list sorted ascending, on the device.
+struct OutageHostScn {
+    std::vector<int64_t> off;
+    std::vector<int32_t> edge;
+    DevBuf doff, dedge;
+    // false: an offset that does not rise or an id that is no edge id
+    bool take(const shd_route* c, const int64_t* scn_off, const int32_t* scn_edge, int32_t nscn) {
+        if (nscn < 0 || (nscn && !scn_off)) return false;
+        off.assign(1, 0);
+        if (!nscn) return true;
+        if (scn_off[0] != 0) return false;
+        for (int k = 0; k < nscn; k++)
+            if (scn_off[k + 1] < scn_off[k]) return false;
+        const int64_t tot = scn_off[nscn];
+        if (tot && !scn_edge) return false;
+        for (int64_t x = 0; x < tot; x++)
+            if (scn_edge[x] < 0 || scn_edge[x] >= c->m) return false;
+        off.assign(scn_off, scn_off + nscn + 1);
+        edge.assign(scn_edge, scn_edge + tot);
+        for (int k = 0; k < nscn; k++) std::sort(edge.begin() + off[k], edge.begin() + off[k + 1]);
+        return true;
+    }
+    int to_device() {
+        int rc;
+        if ((rc = doff.alloc(sizeof(int64_t) * off.size())) || (rc = dedge.alloc(sizeof(int32_t) * std::max<size_t>(edge.size(), 1))))
+            return rc;
+        if (hipMemcpy(doff.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            (!edge.empty() &&
+             hipMemcpy(dedge.p, edge.data(), sizeof(int32_t) * edge.size(), hipMemcpyHostToDevice) != hipSuccess))
+            return SHD_ROUTE_EDEVICE;
+        return SHD_ROUTE_OK;
+    }
+    OutageScn scn() const { return OutageScn{(const int64_t*)doff.p, (const int32_t*)dedge.p, (int)off.size() - 1}; }
+};
+
+// device accumulators of the blocking calls: the statistics, the maxima and unrouted
+struct OutageOut {
+    DevBuf ds, dm, du;
+    int nscn = 0;
+    int init(int nscn_) {
+        nscn = nscn_;
+        const size_t sb = sizeof(uint64_t) * SHD_ROUTE_OUTAGE_NSTAT * (size_t)std::max(nscn, 1);
+        const size_t mb = sizeof(double) * (size_t)std::max(nscn, 1);
+        int rc;
+        if ((rc = ds.alloc(sb)) || (rc = dm.alloc(mb)) || (rc = du.alloc(sizeof(uint64_t)))) return rc;
+        if (hipMemset(ds.p, 0, sb) != hipSuccess || hipMemset(dm.p, 0, mb) != hipSuccess ||
+            hipMemset(du.p, 0, sizeof(uint64_t)) != hipSuccess)
+            return SHD_ROUTE_EDEVICE;
+        return SHD_ROUTE_OK;
+    }
+    OutageOuts outs(double* lat, long long plane) const {
+        return OutageOuts{(unsigned long long*)ds.p, (unsigned long long*)dm.p, lat, plane, (unsigned long long*)du.p};
+    }
+    int finish(uint64_t* stats_out, double* max_add_out, uint64_t* unrouted_out) {
+        int rc;
+        if ((rc = to_host(stats_out, ds.p, sizeof(uint64_t) * SHD_ROUTE_OUTAGE_NSTAT * (size_t)nscn)) ||
+            (rc = to_host(max_add_out, dm.p, sizeof(double) * (size_t)nscn)))
+            return rc;
+        return to_host(unrouted_out, du.p, sizeof(uint64_t));
+    }
+};
+
+// the outputs of a blocking call that has nothing to route
+void ou_host_zero(int32_t nscn, uint64_t* stats_out, double* max_add_out, uint64_t* unrouted_out) {
+    if (stats_out) std::fill(stats_out, stats_out + (size_t)nscn * SHD_ROUTE_OUTAGE_NSTAT, (uint64_t)0);
+    if (max_add_out) std::fill(max_add_out, max_add_out + nscn, 0.0);
+    if (unrouted_out) *unrouted_out = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shd_route_outage_async(shd_route_t* c, const int32_t* d_src, int32_t ns, const int32_t* d_tgt, int32_t nt,
+                           int64_t ld, uint32_t flags, const uint64_t* d_wt, const int64_t* d_scn_off,
+                           const int32_t* d_scn_edge, int32_t nscn, uint64_t* d_stats, double* d_max_add, double* d_lat,
+                           uint64_t* d_unrouted, void* stream) {
+    if (!block_args_ok(c, d_src, ns, d_tgt, nt, ld) || flags != 0u || nscn < 0 || (nscn && !d_scn_off))
+        return SHD_ROUTE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const OutageOuts o{(unsigned long long*)d_stats, (unsigned long long*)d_max_add, d_lat, (long long)ns * ld,
+                       (unsigned long long*)d_unrouted};
+    int rc = ou_zero(o, nscn, st);
+    if (rc || ns == 0 || nt == 0) return rc;
+    if ((rc = ensure_outage(c))) return rc;
+    const OutageScn scn{d_scn_off, d_scn_edge, nscn};
+    if (nscn) {
+        hipLaunchKernelGGL(outage_check_kernel, dim3((unsigned)std::min((nscn + 255) / 256, 1024)), dim3(256), 0, st,
+                           dev_outage(c, scn), c->d_err);
+        if ((rc = hip_check(hipGetLastError()))) return rc;
+    }
+    return ou_sources(c, d_src, ns, d_tgt, nt, (long long)ld, nullptr, d_wt, scn, o, st);
+}
+
+int shd_route_outage(shd_route_t* c, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt, uint32_t flags,
+                     const uint64_t* wt, const int64_t* scn_off, const int32_t* scn_edge, int32_t nscn,
+                     uint64_t* stats_out, double* max_add_out, double* lat_out, uint64_t* unrouted_out) {
+    if (!block_args_ok(c, src, ns, tgt, nt, nt) || flags != 0u) return SHD_ROUTE_EINVAL;
+    for (int32_t i = 0; i < ns; i++)
+        if (src[i] < 0 || src[i] >= c->n) return SHD_ROUTE_EINVAL;
+    for (int32_t j = 0; j < nt; j++)
+        if (tgt[j] < 0 || tgt[j] >= c->n) return SHD_ROUTE_EINVAL;
+    OutageHostScn hs;
+    if (!hs.take(c, scn_off, scn_edge, nscn)) return SHD_ROUTE_EINVAL;
+    if (ns == 0 || nt == 0) {
+        ou_host_zero(nscn, stats_out, max_add_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    const bool want_lat = lat_out && nscn;
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)nt;
+    const int32_t chunk = host_chunk(ns, row_bytes * (want_lat ? (size_t)nscn + 1 : 1));
+    DevBuf dw, dlat;
+    OutageOut out;
+    int rc;
+    if ((wt && (rc = dw.alloc(row_bytes * chunk))) || (want_lat && (rc = dlat.alloc(row_bytes * chunk * nscn))) ||
+        (rc = hs.to_device()) || (rc = out.init(nscn)))
+        return rc;
+    std::vector<double> stage;
+    return host_blocks(
+        c, src, ns, tgt, nt, chunk,
+        [&](int32_t i0, int32_t k, const int32_t* d_src, const int32_t* d_tgt) {
+            if (wt && hipMemcpy(dw.p, wt + (size_t)i0 * nt, row_bytes * k, hipMemcpyHostToDevice) != hipSuccess)
+                return SHD_ROUTE_EDEVICE;
+            return ou_sources(c, d_src, k, d_tgt, nt, nt, nullptr, wt ? (const uint64_t*)dw.p : nullptr, hs.scn(),
+                              out.outs(want_lat ? (double*)dlat.p : nullptr, (long long)k * nt), nullptr);
+        },
+        [&](int32_t i0, int32_t k) {
+            if (want_lat) {  // the chunk's planes [scenario][k][nt] into the caller's [scenario][ns][nt]
+                stage.resize((size_t)nscn * k * nt);
+                if (int r = to_host(stage.data(), dlat.p, sizeof(double) * stage.size())) return r;
+                for (int32_t q = 0; q < nscn; q++)
+                    std::memcpy(lat_out + ((size_t)q * ns + i0) * nt, stage.data() + (size_t)q * k * nt, row_bytes * k);
+            }
+            return i0 + k < ns ? SHD_ROUTE_OK : out.finish(stats_out, max_add_out, unrouted_out);
+        });
+}
+
+int shd_route_pair_outage(shd_route_t* c, const int32_t* pair_src, const int32_t* pair_tgt, const uint64_t* pair_wt,
+                          int64_t npairs, uint32_t flags, const int64_t* scn_off, const int32_t* scn_edge, int32_t nscn,
+                          uint64_t* stats_out, double* max_add_out, double* lat_out, uint64_t* unrouted_out) {
+    if (!pair_args_ok(c, pair_src, pair_tgt, npairs) || !pairs_in_range(c, pair_src, pair_tgt, (int)npairs) ||
+        flags != 0u)
+        return SHD_ROUTE_EINVAL;
+    OutageHostScn hs;
+    if (!hs.take(c, scn_off, scn_edge, nscn)) return SHD_ROUTE_EINVAL;
+    const int np = (int)npairs;
+    if (np == 0) {
+        ou_host_zero(nscn, stats_out, max_add_out, unrouted_out);
+        return SHD_ROUTE_OK;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return SHD_ROUTE_EDEVICE;
+    // the entries of distinct source u are the grouped positions first[u] .. first[u + 1]
+    const PairGroups pg = group_pairs(pair_src, pair_tgt, pair_wt, np);
+    const int nu = (int)pg.us.size();
+    const bool want_lat = lat_out && nscn;
+    DevBuf dsrc, dtgt, dw, doff, dlat;
+    OutageOut out;
+    int rc;
+    if ((rc = dsrc.alloc(sizeof(int32_t) * nu)) || (rc = dtgt.alloc(sizeof(int32_t) * (size_t)np)) ||
+        (pair_wt && (rc = dw.alloc(sizeof(uint64_t) * (size_t)np))) ||
+        (rc = doff.alloc(sizeof(long long) * ((size_t)nu + 1))) ||
+        (want_lat && (rc = dlat.alloc(sizeof(double) * (size_t)np * nscn))) || (rc = hs.to_device()) ||
+        (rc = out.init(nscn)))
+        return rc;
+    if (hipMemcpy(dsrc.p, pg.us.data(), sizeof(int32_t) * nu, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dtgt.p, pg.gt.data(), sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess ||
+        (pair_wt && hipMemcpy(dw.p, pg.gw.data(), sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(doff.p, pg.first.data(), sizeof(long long) * ((size_t)nu + 1), hipMemcpyHostToDevice) != hipSuccess)
+        return SHD_ROUTE_EDEVICE;
+    SoftCode sc;
+    if ((rc = ou_sources(c, (const int32_t*)dsrc.p, nu, (const int32_t*)dtgt.p, 0, 0, (const long long*)doff.p,
+                         pair_wt ? (const uint64_t*)dw.p : nullptr, hs.scn(),
+                         out.outs(want_lat ? (double*)dlat.p : nullptr, (long long)np), nullptr)) ||
+        (rc = sc.sync(c)))
+        return rc;
+    if (want_lat) {  // back to the caller's pair order
+        std::vector<double> grouped((size_t)np * nscn);
+        if ((rc = to_host(grouped.data(), dlat.p, sizeof(double) * grouped.size()))) return rc;
+        for (int32_t q = 0; q < nscn; q++)
+            for (int gq = 0; gq < np; gq++) lat_out[(size_t)q * np + pg.order[gq]] = grouped[(size_t)q * np + gq];
+    }
+    if ((rc = out.finish(stats_out, max_add_out, unrouted_out))) return rc;
     return sc.soft;
 }
 

@@ -97,8 +97,8 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 }
 
 // ---- the form of a per-source state kernel ----
-// hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, loss_tree_kernel, ties_dag_kernel and
-// ecmp_dag_kernel keep one source's state per workgroup:
+// hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, loss_tree_kernel, ties_dag_kernel,
+// ecmp_dag_kernel and outage_repair_kernel (k = its work units) keep one source's state per workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
 // else u16 (n <= 65535) or u32 state in HBM slices, one per resident workgroup.
@@ -162,6 +162,12 @@ struct PathDev {
     int lo_ready = 0;
     double* lo_r = nullptr; double* lo_q = nullptr; double* lo_p = nullptr;
     PathSlices lo_ws;
+    // link outages: per edge id its ends and its latency, per vertex its self-loop edge ids
+    // (offsets and ids, ascending), built at the first outage call; and the HBM slices
+    int ou_ready = 0;
+    int* ou_ea = nullptr; int* ou_eb = nullptr; double* ou_lat = nullptr;
+    int* ou_srow = nullptr; int* ou_seid = nullptr;
+    PathSlices ou_ws;
 };
 
 }  // namespace shd

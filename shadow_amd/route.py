@@ -31,6 +31,7 @@ FILL_LAT16 = 0x100
 LOADS_ADD = 0x400  # shd_route.h SHD_ROUTE_LOADS_ADD
 FOLD_SUM, FOLD_MIN, FOLD_MAX, FOLD_PROD = 0, 1, 2, 3  # SHD_ROUTE_FOLD_*
 FOLD_MAX_N = 8
+OUTAGE_HIT, OUTAGE_CUT, OUTAGE_SLOWER, OUTAGE_NSTAT = 0, 1, 2, 3  # SHD_ROUTE_OUTAGE_*
 
 
 class RouteError(RuntimeError):
@@ -91,6 +92,7 @@ EXPORTS = (
     "shd_route_ecmp_loads_async", "shd_route_ecmp_loads", "shd_route_pair_ecmp_loads",
     "shd_route_fold_async", "shd_route_fold", "shd_route_pair_fold",
     "shd_route_loss_async", "shd_route_loss", "shd_route_pair_loss",
+    "shd_route_outage_async", "shd_route_outage", "shd_route_pair_outage",
 )
 
 _lib = None
@@ -191,6 +193,12 @@ def load_library():
     L.shd_route_loss.argtypes = [P, P, I32, P, I32, U32, P, P, P, P, P, P]
     L.shd_route_pair_loss.restype = C.c_int
     L.shd_route_pair_loss.argtypes = [P, P, P, P, I64, U32, P, P, P, P, P]
+    L.shd_route_outage_async.restype = C.c_int
+    L.shd_route_outage_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, I32, P, P, P, P, P]
+    L.shd_route_outage.restype = C.c_int
+    L.shd_route_outage.argtypes = [P, P, I32, P, I32, U32, P, P, P, I32, P, P, P, P]
+    L.shd_route_pair_outage.restype = C.c_int
+    L.shd_route_pair_outage.argtypes = [P, P, P, P, I64, U32, P, P, I32, P, P, P, P]
     L.shd_route_fold_async.restype = C.c_int
     L.shd_route_fold_async.argtypes = [P, P, I32, P, I32, I64, U32, P, I32, P, P, I64, P]
     L.shd_route_fold.restype = C.c_int
@@ -210,6 +218,20 @@ def strerror(code: int) -> str:
 
 def _p(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def pack_scenarios(scenarios):
+    """(off int64, edge int32) of a list of id arrays or of an (off, edge) tuple of arrays."""
+    if isinstance(scenarios, tuple):
+        off = np.ascontiguousarray(scenarios[0], np.int64)
+        edge = np.ascontiguousarray(scenarios[1], np.int32).reshape(-1)
+    else:
+        lists = [np.asarray(f, np.int32).reshape(-1) for f in scenarios]
+        off = np.zeros(len(lists) + 1, np.int64)
+        if lists:
+            off[1:] = np.cumsum([len(f) for f in lists])
+        edge = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, np.int32)
+    return off, np.ascontiguousarray(edge)
 
 
 def _check(rc, what):
@@ -504,6 +526,62 @@ class RouteEngine:
         _check(rc, "shd_route_pair_loss")
         return res
 
+    def _outage_out(self, nscn, entries, lat, out):
+        if out is not None:
+            return out
+        return (np.zeros((nscn, OUTAGE_NSTAT), np.uint64), np.zeros(nscn, np.float64),
+                np.full((nscn, *entries), np.nan) if lat else None, np.zeros(1, np.uint64))
+
+    def outage(self, sources, targets, scenarios, weights=None, lat: bool = False, out=None):
+        """shd_route_outage: (stats, max_add, lat, unrouted) of the (source, target) block under
+        every scenario, each a set of failed edge ids: scenarios is a list of id arrays or an
+        (off, edge) tuple of arrays.  stats is uint64 (scenarios, OUTAGE_NSTAT) with the columns
+        OUTAGE_HIT, OUTAGE_CUT and OUTAGE_SLOWER, max_add float64 per scenario; lat=True also
+        returns the new latencies (scenarios, sources, targets), NaN where cut or failed, else
+        None.  Entries are judged without dispatch.  weights as loads().  out: the four arrays
+        of an earlier call's shapes (unrouted a 1-element uint64 array), any of them None for an
+        output not wanted.  A missing self-loop or an unreachable target in the whole graph raises
+        RouteError; ``err.partial`` then holds the results."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        off, edge = pack_scenarios(scenarios)
+        nscn = len(off) - 1
+        st, mx, la, un = self._outage_out(nscn, (len(s), len(t)), lat, out)
+        rc = load_library().shd_route_outage(self._h, _p(s), len(s), _p(t), len(t), 0, _p(w), _p(off), _p(edge), nscn,
+                                             _p(st), _p(mx), _p(la), _p(un))
+        res = (st, mx, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_outage")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_outage")
+        return res
+
+    def pair_outage(self, pair_src, pair_tgt, scenarios, pair_wt=None, lat: bool = False, out=None):
+        """shd_route_pair_outage: as outage() for a list of (source, target, weight) pairs in any
+        order, repeats adding up (pair_wt None = 1 each); lat is (scenarios, pairs) in the
+        caller's pair order."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        off, edge = pack_scenarios(scenarios)
+        nscn = len(off) - 1
+        st, mx, la, un = self._outage_out(nscn, (len(s),), lat, out)
+        rc = load_library().shd_route_pair_outage(self._h, _p(s), _p(t), _p(w), len(s), 0, _p(off), _p(edge), nscn,
+                                                  _p(st), _p(mx), _p(la), _p(un))
+        res = (st, mx, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_outage")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_pair_outage")
+        return res
+
     def _fold_args(self, ops, values):
         o = np.ascontiguousarray(ops, np.int32).reshape(-1)
         v = np.ascontiguousarray(values, np.float64)
@@ -564,6 +642,22 @@ class RouteEngine:
             self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, DISPATCH if dispatch else 0, _p(o), len(o), ptr(d_val),
             ptr(d_out), plane, C.c_void_p(stream) if stream else None)
         _check(rc, "shd_route_fold_async")
+
+    def outage_async(self, d_src, d_tgt, d_wt, d_scn_off, d_scn_edge, d_stats, d_max_add, d_lat, d_unrouted,
+                     stream=None, ld=None, flags=0):
+        """shd_route_outage_async over device tensors: int32 sources and targets, 64-bit integer
+        weights (None = 1 per entry), int64 scenario offsets (scenarios + 1) and int32 edge ids,
+        each scenario ascending; 64-bit integer stats (scenarios x OUTAGE_NSTAT), float64
+        max_add (scenarios) and lat (scenarios x sources x ld), a 64-bit integer unrouted (1
+        element); any output may be None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        nscn = 0 if d_scn_off is None else int(d_scn_off.numel()) - 1
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_outage_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, int(flags), ptr(d_wt), ptr(d_scn_off), ptr(d_scn_edge), nscn,
+            ptr(d_stats), ptr(d_max_add), ptr(d_lat), ptr(d_unrouted), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_outage_async")
 
     def loss_async(self, d_src, d_tgt, d_wt, d_edge_reach, d_edge_drop, d_vertex_drop, d_delivered, d_unrouted,
                    stream=None, dispatch=True, ld=None, add=False):

@@ -31,7 +31,7 @@ EXPORTS = (
     "shd_topology_get_path", "shd_topology_format_path", "shd_topology_dump_routes", "shd_topology_route_line",
     "shd_topology_link_loads", "shd_topology_ecmp_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
-    "shd_topology_edge_jitter", "shd_topology_fold_pairs", "shd_topology_link_loss",
+    "shd_topology_edge_jitter", "shd_topology_fold_pairs", "shd_topology_link_loss", "shd_topology_link_outage",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
@@ -116,6 +116,8 @@ def load_library():
     L.shd_topology_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_ecmp_link_loads.restype = C.c_int
     L.shd_topology_ecmp_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_link_outage.restype = C.c_int
+    L.shd_topology_link_outage.argtypes = [P, P, P, C.c_int32, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_link_loss.restype = C.c_int
     L.shd_topology_link_loss.argtypes = [P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_edge_jitter.restype = C.c_int
@@ -421,6 +423,25 @@ class Topology:
         if rc:
             raise RuntimeError(f"link_loss failed ({rc})")
         return er, ed, vd, dl, int(un.value)
+
+    def link_outage(self, scenarios):
+        """shd_topology_link_outage: (stats, max_add, unrouted) of the cached Paths' packet counters
+        under every scenario of failed edge ids (a list of id arrays, or an (off, edge) tuple):
+        uint64 stats (scenarios, 3) = the packets hit, cut off and slower, float64 max_add per
+        scenario, an exact integer unrouted.  Raises RuntimeError with SHD_ROUTE_EUNSUPPORTED (-6)
+        for a topology whose cache dispatches (a complete graph, or prefer-direct)."""
+        from .route import pack_scenarios
+        L = load_library()
+        off, edge = pack_scenarios(scenarios)
+        nscn = len(off) - 1
+        st, mx = np.zeros((nscn, 3), np.uint64), np.zeros(nscn, np.float64)
+        un = C.c_uint64()
+        rc = L.shd_topology_link_outage(self._h, C.c_void_p(off.ctypes.data), C.c_void_p(edge.ctypes.data) if len(edge)
+                                        else None, nscn, C.c_void_p(st.ctypes.data), C.c_void_p(mx.ctypes.data),
+                                        C.byref(un))
+        if rc:
+            raise RuntimeError(f"link_outage failed ({rc})")
+        return st, mx, int(un.value)
 
     def edge_jitter(self):
         """shd_topology_edge_jitter: the graphml's jitter edge attribute per edge id (NaN where
