@@ -79,9 +79,11 @@ class _Acc:
 
 
 class LossRef:
-    def __init__(self, g):
+    def __init__(self, g, tie: str = "low"):
+        """tie="high" is the mutant that takes the highest edge id among the tight parallel arcs
+        of a hop (multi_ref.Ref's), which tests/test_frac_graphs.py must see on frac_multi."""
         self.g = g
-        self.ref = Ref(g)
+        self.ref = Ref(g, tie)
         self.n, self.m = self.ref.n, int(g.m)
         self.q = np.asarray(g.packetloss, np.float64).tolist()
         self.r = self.ref.erel.tolist()

@@ -24,6 +24,12 @@ from tests.multi_ref import Ref
 HIT, CUT, SLOWER, NSTAT = 0, 1, 2, 3
 ENOEDGE, EUNREACH = -4, -5         # SHD_ROUTE_ENOEDGE, SHD_ROUTE_EUNREACH (checked in test_outage.py)
 MUTANTS = ("roots_only", "seed_marked", "one_sweep", "one_arc", "hit_is_changed")
+# wrong only in the last bits of a double, which integer latencies never show: tests/test_frac_graphs.py
+# holds them to the fractional builders.  slower_tol judges SLOWER as new > old + 1e-12;
+# root_offset rebuilds the distance of a marked vertex below its root as
+# dnew[root] + (old[v] - old[root]) wherever the vertex keeps its way down from the root (the
+# shifted value lies within 4 ulp of the left fold), instead of taking the left fold itself
+FRAC_MUTANTS = ("slower_tol", "root_offset")
 MASK = (1 << 64) - 1
 
 # ---- the layout and the units (outage_layout.hpp) -------------------------------------------------
@@ -273,6 +279,17 @@ class OutageRef:
                 break
         if sweeps > 2:
             self.seen.add("many_sweeps")
+        if mutant == "root_offset":
+            top = {}                                          # the root a marked vertex hangs below
+            for v in A:                                       # level order: a parent comes first
+                top[v] = v if v in roots else top[int(pu[v])]
+            true = dict(dn)
+            for v in A:
+                r = top[v]
+                if v != r and np.isfinite(true[r]) and np.isfinite(true[v]):
+                    cand = true[r] + (d[v] - d[r])
+                    if abs(cand - true[v]) <= 4 * np.spacing(true[v]):
+                        dn[v] = cand
         return dn, A
 
     @staticmethod
@@ -318,7 +335,7 @@ class OutageRef:
                         acc[HIT] += w
                     if np.isnan(nw):
                         acc[CUT] += w
-                    elif nw > o:
+                    elif (nw > o + 1e-12) if mutant == "slower_tol" else (nw > o):
                         acc[SLOWER] += w
                         mx[k] = max(mx[k], nw - o)
             stats[k] = [a & MASK for a in acc]

@@ -24,6 +24,15 @@ Per tied builder, over the sources of frac_graphs.sources:
                reliability product along the routes; on the simple builders it changes nothing,
                which is asserted as well.
 
+Link outages and link loss (the scenario rule and the weight block test_frac_paths_gpu.py uses):
+  outages      no entry fails and no scenario cuts anything (every reduced graph has a context);
+               at least three tied builders have a scenario with HIT > SLOWER (a tied detour), and
+               frac_multi one with HIT > 0 and SLOWER == 0 (the failed edge has a tied twin); some
+               scenario's max_add lies in (0, 2^-50): entries that get slower by an ulp
+  mutants      SLOWER judged with a tolerance, a repaired distance rebuilt from its root's instead
+               of folded from the source, and LossRef over the highest tight edge id of a hop:
+               each changes an asserted output
+
 The last section pins the premise the path calls rest on (the tight arcs form a DAG because
 d[u] + w > d[u]) on a chain whose latencies are absorbed, and the host-side refusal of
 shd_route_create that keeps such a graph away from every kernel.
@@ -37,6 +46,8 @@ import pytest
 from shadow_amd.graph import Graph, config
 from tests import ecmp_ref as er
 from tests import frac_graphs as fg
+from tests import loss_ref as lr
+from tests import outage_ref as orf
 from tests.multi_ref import Ref
 from tests.ties_ref import TiesRef
 
@@ -318,6 +329,83 @@ def test_ties_ref_counts_are_the_rule():
         for s, d, pa, cnt, fs in base(name)[:4]:
             c = list(T.dag(s)[0])
             assert c == cnt
+
+
+# ---- link outages and link loss on the builders -------------------------------------------------------
+
+def path_weights(name):
+    """The fixed weight block of test_frac_paths_gpu.py: 1 .. 2^40 per (source, vertex)."""
+    g = fg.get(name)
+    return np.random.default_rng(g.n).integers(1, 1 << 40, size=(len(fg.sources(name)), g.n), dtype=np.uint64)
+
+
+def outage_scenarios(name):
+    """The scenario rule: the edge ids of the reference's route from the first to the last source,
+    the first six singly, the first two together, and the empty scenario."""
+    S = fg.sources(name)
+    es = [int(e) for e in ref_of(name).path(int(S[0]), int(S[-1]))[1]]
+    assert es
+    return [[e] for e in es[:6]] + ([sorted(es[:2])] if len(es) >= 2 else []) + [[]]
+
+
+@functools.lru_cache(maxsize=None)
+def outage_case(name):
+    """(OutageRef, scenarios, the programme's Result) of the builder's sources over every vertex
+    under the scenario rule, weighted with path_weights."""
+    g = fg.get(name)
+    O = orf.OutageRef(g)
+    scn = outage_scenarios(name)
+    S, T = fg.sources(name), np.arange(g.n, dtype=np.int32)
+    return O, scn, O.repair(*orf.block_entries(S, T, path_weights(name)), scn)
+
+
+def test_outage_scenarios_have_ties_and_ulp_steps():
+    """What test_frac_paths_gpu.py relies on: nothing fails, nothing is cut (so every reduced
+    graph is connected and has a context), and the scenarios hold tied detours and entries that
+    get slower by less than 2^-50."""
+    detour, twin, small = [], [], []
+    for name in fg.SUITE:
+        O, scn, r = outage_case(name)
+        st = r.stats.astype(object)
+        print(f"{name}: scenarios {scn}, HIT/CUT/SLOWER {st.tolist()}, max_add {r.max_add.tolist()}")
+        assert r.codes == frozenset({0}) and r.unrouted == 0 and not np.isnan(r.lat).any()
+        assert not r.stats[:, orf.CUT].any() and scn[-1] == [] and not r.stats[-1].any()
+        assert 2 <= len(scn) <= 8 and r.stats[:-1, orf.HIT].all()        # (frac_hub's route is one biclique edge)
+        for k in range(len(scn) - 1):
+            if st[k][orf.HIT] > st[k][orf.SLOWER]:
+                detour.append(name)
+            if st[k][orf.HIT] > 0 and st[k][orf.SLOWER] == 0:
+                twin.append(name)
+            if 0 < r.max_add[k] < 2.0 ** -50:
+                small.append((name, float(r.max_add[k])))
+    assert len(set(detour) & set(fg.TIED)) >= 3 and "frac_multi" in twin
+    assert small and ("frac_hub", 2.0 ** -54) in small
+
+
+@pytest.mark.parametrize("mutant", orf.FRAC_MUTANTS)
+def test_outage_mutants_differ(mutant):
+    seen = []
+    for name in fg.SUITE:
+        O, scn, r = outage_case(name)
+        S, T = fg.sources(name), np.arange(fg.get(name).n, dtype=np.int32)
+        bad = O.repair(*orf.block_entries(S, T, path_weights(name)), scn, mutant=mutant)
+        if not bad.same(r):
+            seen.append(name)
+    print(mutant, seen)
+    assert seen, mutant
+
+
+def test_loss_highest_edge_id_mutant():
+    """LossRef over Ref(g, tie="high"): on frac_multi a tight hop with a tied twin of another loss
+    changes the expected drops; on a simple builder it cannot."""
+    for name, differs in (("frac_multi", True), ("frac_grid", False)):
+        g = fg.get(name)
+        S, T, W = fg.sources(name), np.arange(g.n, dtype=np.int32), path_weights(name)
+        a, b = lr.LossRef(g).block(S, T, W), lr.LossRef(g, tie="high").block(S, T, W)
+        same = all(np.array_equal(x, y) for x, y in zip(a.arrays(), b.arrays()))
+        assert same != differs, name
+        if differs:
+            assert not np.array_equal(a.arrays()[1], b.arrays()[1]) and not np.array_equal(a.arrays()[3], b.arrays()[3])
 
 
 # ---- absorbed latencies: the premise, and the refusal that keeps it ---------------------------------

@@ -1,7 +1,7 @@
-"""GPU: the five families of path calls -- hops / routes / loads, the tie envelope, the ECMP loads
-and the path folds -- on the fractional-latency graphs of tests/frac_graphs.py, whose shortest
-paths tie or miss a tie by an ulp in f64 (tests/test_frac_graphs.py holds the builders to that).
-All of them read the chosen paths out of finished distance rows by one rule: an arc u -> v is on
+"""GPU: the seven families of path calls -- hops / routes / loads, the tie envelope, the ECMP loads,
+the path folds, the link loss and the link outages -- on the fractional-latency graphs of
+tests/frac_graphs.py, whose shortest paths tie or miss a tie by an ulp in f64
+(tests/test_frac_graphs.py holds the builders to that).  All of them read the chosen paths out of finished distance rows by one rule: an arc u -> v is on
 a shortest path exactly when d[u] + w == d[v] in double.  A kernel that compares with a tolerance,
 sums in another order, or reads a latency through another conversion than the rows kernel did
 (KFH's packed k / scale arcs against the f64 in-CSR of the path calls, the out-CSR copy of a
@@ -17,7 +17,8 @@ Every builder runs under four rows selections, each asserted through eng.info --
   f64       SHD_ROUTE_KERNEL=f64                     the generic kernel (kernel 0)
 
 -- and in both state forms of every path call ("lds": no knob; "hbm": SHD_ROUTE_HOPS_LDS,
-LOADS_LDS, TIES_LDS, ECMP_LDS and FOLD_LDS all 0): the whole cross product, a few tenths of a second a case.
+LOADS_LDS, TIES_LDS, ECMP_LDS, FOLD_LDS, LOSS_LDS and OUTAGE_LDS all 0): the whole cross product,
+up to half a second a case.
 About 24 sources spread over the graph, every vertex a target.
 
 What is compared, and how:
@@ -29,9 +30,21 @@ What is compared, and how:
   folds                 sum / min / max of the latency column and the product of 1 - loss in one
                         call, to the bit against fold_ref (test_fold_gpu.check); the sum is the
                         rows' lat, the product the rows' rel where neither end has a vertex factor
-  across selections     hops, routes, loads, ties and folds are array_equal to the default
-                        selection's.  The ECMP loads are compared within twice the derived
-                        tolerance: a vertex's state is a fixed-order sum, but the per-source
+  loss                  the weighted block within loss_ref's derived bound (R + 4 + A) * 2^-52 of the
+                        exact fractions; six one-source calls bit-equal to the plain f64 programme
+                        (no element takes more than two addends); with unit weights delivered is
+                        the rows' rel where neither end has a vertex factor
+  outages               the scenarios of tests/test_frac_graphs.py (the edges of the route from the
+                        first to the last source, singly and the first two together, and none):
+                        stats, max_add, unrouted and every new latency equal outage_ref.OutageRef
+                        exactly.  SLOWER is new > old in f64, max_add one f64 subtraction, and some
+                        entries get slower by exactly one ulp (frac_hub: 2^-54).  In the "lds" form
+                        up to three scenarios are also held to a context created from the reduced
+                        graph under the same selection: lat[k] is bit-equal to its rows
+  across selections     hops, routes, loads, ties, folds, the outage outputs and the one-source loss
+                        outputs are array_equal to the default selection's; the block loss outputs
+                        within twice their bound, as the ECMP loads are.  The ECMP loads are compared
+                        within twice the derived tolerance: a vertex's state is a fixed-order sum, but the per-source
                         contributions reach the output arrays by floating-point atomic adds, whose
                         order is not fixed from launch to launch.
 """
@@ -43,8 +56,11 @@ import pytest
 from shadow_amd.graph import to_graphml
 from tests import fold_ref as fr
 from tests import frac_graphs as fg
+from tests import loss_ref as lr
+from tests import outage_ref as orf
 from tests import test_ecmp_gpu as eg
 from tests import test_fold_gpu as dg
+from tests import test_frac_graphs as tfg
 from tests import test_hops_gpu as hg
 from tests import test_ties_gpu as tg
 from tests.multi_ref import Ref
@@ -60,7 +76,9 @@ SELECTIONS = {
     "f64": {"SHD_ROUTE_KERNEL": "f64"},
 }
 FORM_KNOBS = ("SHD_ROUTE_HOPS_LDS", "SHD_ROUTE_LOADS_LDS", "SHD_ROUTE_TIES_LDS", "SHD_ROUTE_ECMP_LDS",
-              "SHD_ROUTE_FOLD_LDS")
+              "SHD_ROUTE_FOLD_LDS", "SHD_ROUTE_LOSS_LDS", "SHD_ROUTE_OUTAGE_LDS")
+LOSS_ONE = 6        # one-source loss calls per builder
+REDUCED = 3         # scenarios held to a context of the reduced graph
 OPS = [fr.SUM, fr.MIN, fr.MAX, fr.PROD]
 
 
@@ -154,13 +172,24 @@ def reference(name):
     vf = R.vf
     plain = np.isnan(vf)[S][:, None] & np.isnan(vf)[None, :]  # neither end has a vertex factor
     bare = np.isnan(vf)[None, :] | (T[None, :] == S[:, None])  # no factor of the target's to place
+    # link loss: the weighted block in exact fractions, LOSS_ONE one-source calls in plain f64
+    assert np.array_equal(W, tfg.path_weights(name))
+    L = lr.LossRef(g)
+    loss = L.block(S, T, W, exact=True)
+    one_at = np.unique(np.linspace(0, len(S) - 1, LOSS_ONE).astype(int))
+    loss_one = [L.block(S[i:i + 1], T, W[i:i + 1]) for i in one_at.tolist()]
+    assert not loss.codes and loss.unrouted == 0 and loss.A > 2 and all(o.A <= 2 and not o.codes for o in loss_one)
+    # link outages: the scenario rule and the programme's result of tests/test_frac_graphs.py
+    _, scn, outage = tfg.outage_case(name)
+    assert outage.codes == frozenset({0}) and not outage.stats[:, orf.CUT].any()
     return dict(g=g, R=R, S=S, T=T, lat=lat, rel=rel, hops=hops, ps=ps, pt=pt, routes=routes, W=W, loads=loads,
-                cnt=cnt, plain=plain, bare=bare)
+                cnt=cnt, plain=plain, bare=bare, loss=loss, one_at=one_at, loss_one=loss_one, scn=scn, outage=outage)
 
 
-def run_all(route, name):
+def run_all(route, name, form):
     """Every path call of one context against its reference; the outputs for the comparison
-    across selections."""
+    across selections.  form "lds": also the outage's new latencies against contexts of the
+    reduced graphs, created under the selection in force."""
     ref = reference(name)
     g, S, T = ref["g"], ref["S"], ref["T"]
     eng = route.RouteEngine(g)
@@ -215,6 +244,39 @@ def run_all(route, name):
     assert np.all(fold[1] <= fold[2]) and np.all(fold[2] <= fold[0])
     assert np.array_equal(fold[3][ref["plain"]], rel[ref["plain"]])
     out.update(fold=fold)
+    # link loss: the block, the one-source calls, unit weights
+    want = ref["loss"]
+    lb, c = call(route, eng.loss, S, T, ref["W"], dispatch=False)
+    assert c == route.OK and lb[4] == 0
+    for k in range(4):
+        assert lr.close(lb[k], want.outs()[k], want.R, want.A), (lr.NAMES[k], want.R, want.A)
+    ones = []
+    for i, w1 in zip(ref["one_at"].tolist(), ref["loss_one"]):
+        lo1, c = call(route, eng.loss, S[i:i + 1], T, ref["W"][i:i + 1], dispatch=False)
+        assert c == route.OK and lo1[4] == 0
+        for k in range(4):
+            assert np.array_equal(lo1[k], w1.arrays()[k]), (int(S[i]), lr.NAMES[k])
+        ones.append(np.concatenate(lo1[:4]))
+    i = len(S) // 2
+    lu, c = call(route, eng.loss, S[i:i + 1], T, None, dispatch=False)
+    assert c == route.OK and np.array_equal(lu[3][ref["plain"][i]], rel[i][ref["plain"][i]])
+    out.update(loss=lb[:4], loss_one=np.stack(ones))
+    # link outages
+    scn, wo = ref["scn"], ref["outage"]
+    (st, mx, nl, un), c = call(route, eng.outage, S, T, scn, ref["W"], lat=True)
+    assert c == route.OK and un == wo.unrouted == 0
+    assert np.array_equal(st, wo.stats) and np.array_equal(mx, wo.max_add), (st.tolist(), mx.tolist())
+    assert np.array_equal(nl, wo.lat.reshape(len(scn), len(S), len(T)))
+    assert np.array_equal(nl[-1], lat) and scn[-1] == []      # no failed edge: the rows themselves
+    out.update(ostats=st, omax=mx, olat=nl)
+    if form == "lds":
+        for k, f in [(k, f) for k, f in enumerate(scn) if f][:REDUCED]:
+            assert wo.stats[k, orf.HIT] > 0 and wo.stats[k, orf.CUT] == 0
+            ek = route.RouteEngine(orf.reduced(g, f))
+            assert ek.info["kernel"] == eng.info["kernel"] and ek.info["lds_resident"] == eng.info["lds_resident"]
+            (rl, _, _), c = call(route, ek.rows, S, T, dispatch=False)
+            assert c == route.OK and np.array_equal(nl[k], rl), (name, k, f)
+            ek.close()
     return out
 
 
@@ -226,7 +288,7 @@ def base_outputs(route, monkeypatch, name, form):
     if (name, form) not in _BASE:
         with monkeypatch.context() as m:
             choose(m, "default", form)
-            _BASE[name, form] = run_all(route, name)
+            _BASE[name, form] = run_all(route, name, form)
     return _BASE[name, form]
 
 
@@ -239,13 +301,15 @@ def test_path_calls(route, monkeypatch, name, sel, form):
     if sel == "default":
         if form == "hbm":                                     # the two state forms against each other
             lds = base_outputs(route, monkeypatch, name, "lds")
-            for k in ("hops", "poff", "vert", "edge", "el", "trn", "cnt", "lo", "hi", "fold"):
+            for k in ("hops", "poff", "vert", "edge", "el", "trn", "cnt", "lo", "hi", "fold", "loss_one", "ostats",
+                      "omax", "olat"):
                 assert np.array_equal(base[k], lds[k], equal_nan=True), k
         return
     choose(monkeypatch, sel, form)
-    got = run_all(route, name)
+    got = run_all(route, name, form)
     expect_info(name, sel, got["info"])
-    for k in ("lat", "hops", "poff", "vert", "edge", "el", "trn", "cnt", "lo", "hi", "fold"):
+    for k in ("lat", "hops", "poff", "vert", "edge", "el", "trn", "cnt", "lo", "hi", "fold", "loss_one", "ostats", "omax",
+              "olat"):
         assert np.array_equal(got[k], base[k], equal_nan=True), k
     bare = reference(name)["bare"]                            # (the rows' rel is no path call: see run_all)
     assert np.array_equal(got["rel"][bare], base["rel"][bare])
@@ -258,6 +322,10 @@ def test_path_calls(route, monkeypatch, name, sel, form):
     for a, b in zip(got["e3"], base["e3"]):
         assert np.array_equal(a, b)                           # whole numbers below 2^53: any order
     print(f"{name} {sel} {form}: ECMP loads bit-equal to the default selection's: {exact}")
+    want = reference(name)["loss"]
+    b2 = float(2 * lr.bound(want.R, want.A))
+    for a, b in zip(got["loss"], base["loss"]):
+        assert np.array_equal(a == 0, b == 0) and np.all(np.abs(a - b) <= b2 * b), "loss"
 
 
 # ---- the pair forms ---------------------------------------------------------------------------------

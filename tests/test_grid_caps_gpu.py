@@ -13,6 +13,13 @@ a graph of a few hundred vertices:
   fw_parent8_kernel                                     2048 x 8        16384 + 9 (ragged last group)
   hops_depth / loads_tree / ties_dag kernels, LDS       1024 per chunk  1024 + 7
   the same three, HBM slices                            512 slots       1024 + 7
+  ecmp_dag / fold_tree / loss_tree kernels, LDS         1024 per chunk  1024 + 7
+  the same three, HBM slices                            512 slots       1024 + 7
+  the same three under dispatch (complete: no state)    1024 per chunk  1024 + 7
+  outage_repair_kernel (grid over work units), LDS      1024 units      1031 sources x 1 slab of 3;
+                                                                        7 sources x 147 slabs of 1
+  the same, HBM slices                                  512 slots       the same 1031 and 1029 units
+  the four pair forms (grouped by distinct source)      1024 per chunk  1056 distinct sources
   hops_parent_kernel, the ties in-degree kernel grid.y  65535           65535 + 5
   direct_rows_kernel (dispatch, shd_route_direct)       65535           65535 + 7
   tri_payload_kernel                                    8192 rows       8192 + 7
@@ -22,7 +29,13 @@ a graph of a few hundred vertices:
 Method: a base list of distinct sources repeated and permuted to cap + r entries; the oracle
 (TIE_MINKEY), tests/ties_ref.py or the loads reference below for the distinct sources only,
 gathered by index; np.array_equal on every output, row reductions included.  The graphs have
-no vertex loss and the listed entries do not fail, so every form is bit-exact.  The calls go
+no vertex loss and the listed entries do not fail, so every form is bit-exact.  The folds and
+the outages are held the same way (fold_ref, outage_ref; the outage statistics are u64 sums,
+linear in the weights, so the reference runs over the distinct sources with each one's rows
+added up).  The ECMP loads and the link loss add floating-point terms across sources in no fixed
+order: they are held to ecmp_ref and loss_ref over the whole repeated list within the two bounds
+those headers derive -- EcmpRef.tol and (R + 4 + A) * 2^-52, R and A counted by the reference for
+the very call -- and exactly where all terms are whole numbers below 2^53.  The calls go
 through the device-pointer entry points (the host wrappers would chunk by output size, not
 below these caps, but stage through buffers of their own), each test asserts that its cap was
 crossed, and where the cap is the context's it is read from tests/select_main.cpp's record.
@@ -37,7 +50,13 @@ import numpy as np
 import pytest
 
 from shadow_amd.graph import complete_graph, internet_like
+from tests import ecmp_ref as er
+from tests import fold_ref as fr
+from tests import loss_ref as lr
+from tests import outage_ref as orf
 from tests import shape_graphs
+from tests import test_hops_gpu as hg
+from tests import test_outage as tout
 from tests import ties_ref as tr
 from tests.test_contexts import selection  # noqa: F401  (select_main's record, built once)
 from tests.test_contract_gpu import close_engines, route  # noqa: F401
@@ -166,6 +185,8 @@ BASE = 48   # distinct sources
 
 @functools.lru_cache(maxsize=None)
 def tree_graph(name):
+    if name in ("k24", "ba80_prefer"):
+        return hg._graph(name)[0]
     return shape_graphs.tiny(6, "all") if name == "path6" else kd_graph(name)
 
 
@@ -250,13 +271,16 @@ def a16(x):
 def crossed(name, what, lds, ns):
     """The launch's grid is below ns: 1024 workgroups in the LDS form, the slot rule in the
     HBM form (state sizes: path_hops.hpp hp_state_bytes, tests/ties_ref.py layout_total,
-    link_loads.hpp's 22 bytes per vertex bounded from above)."""
+    link_loads.hpp's 22 bytes per vertex bounded from above, and the layout_total of ecmp_ref,
+    fold_ref, loss_ref and outage_ref).  ns: the sources; the outage kernel's work units."""
     n = tree_graph(name).n
     assert ns <= (1 << 30) // (16 * n)                # one chunk (hops 12, loads 16 bytes per vertex)
     if lds:
         assert ns > TREE_LDS_CAP
         return
-    stride = {"hops": a16(4 * a16(2 * n)), "ties": a16(tr.layout_total(n, 2)), "loads": a16(32 * n)}[what]
+    stride = {"hops": a16(4 * a16(2 * n)), "ties": a16(tr.layout_total(n, 2)), "loads": a16(32 * n),
+              "ecmp": a16(er.layout_total(n)), "fold": a16(fr.layout_total(n)), "loss": a16(lr.layout_total(n)),
+              "outage": a16(orf.layout_total(n))}[what]
     assert slots_of(stride) == TREE_HBM_SLOTS and ns > 2 * TREE_HBM_SLOTS     # a third source for some
 
 
@@ -472,3 +496,415 @@ def test_kfh(route, oracle_mod, monkeypatch, selection, ring):
     S, idx = repeated(base, ns, 19)
     olat, orel, _, _ = oracle_mod.OracleGraph(g).source_rows(base, T, oracle_mod.TIE_MINKEY)
     check_rows(rows_async(route, eng, S, T), (olat, orel), idx)
+
+
+# ---- ECMP loads, folds, link loss and link outages: the same caps -------------------------------
+# (path_calls.hpp launches ecmp_dag_kernel, fold_tree_kernel, loss_tree_kernel and
+# outage_repair_kernel through state_form as the three above: 1024 workgroups in the LDS form, the
+# slot rule in the HBM form, min(k, 1024) without state under dispatch on a complete graph.)
+
+FAMILY_KNOB = {"ecmp": "SHD_ROUTE_ECMP_LDS", "fold": "SHD_ROUTE_FOLD_LDS", "loss": "SHD_ROUTE_LOSS_LDS",
+               "outage": "SHD_ROUTE_OUTAGE_LDS"}
+FAMILY_REF = {"ecmp": er, "fold": fr, "loss": lr, "outage": orf}
+FOLD_OPS = [fr.SUM, fr.MIN, fr.MAX, fr.PROD]
+
+
+def form(monkeypatch, name, what, lds, ns):
+    """Choose the state form of family `what` and assert that ns crosses its cap in one chunk."""
+    assert FAMILY_REF[what].fits_lds(tree_graph(name).n)     # the LDS form unless the knob says off
+    if not lds:
+        monkeypatch.setenv(FAMILY_KNOB[what], "0")
+    crossed(name, what, lds, ns)
+
+
+def u64(t):
+    return t.cpu().numpy().view(np.uint64)
+
+
+def summed(W, idx, k):
+    """The weight rows W added up per base source (idx: the base index of every row), modulo 2^64."""
+    out = np.zeros((k, W.shape[1]), np.uint64)
+    np.add.at(out, idx, W)
+    return out
+
+
+def load_weights(ns, n, seed):
+    """A u64 block with zeros, a zero row and one value above 2^40 in every other row, as test_loads has."""
+    rng = np.random.default_rng(seed)
+    W = (rng.integers(0, 5, size=(ns, n)) * (rng.random((ns, n)) < 0.3)).astype(np.uint64)
+    W[np.arange(ns), rng.integers(0, n, size=ns)] = np.uint64(2 ** 40 + 3)
+    W[ns // 2] = 0
+    return W
+
+
+# -- folds
+
+@functools.lru_cache(maxsize=None)
+def fold_rows(name, dispatch=False):
+    """((4, base, n) folds of fold_ref.columns, (base, n) latencies of the rows) of the base sources."""
+    g = tree_graph(name)
+    F = fr.FoldRef(g)
+    T = np.arange(g.n, dtype=np.int32)
+    out, codes = F.rows(tree_base(name), T, FOLD_OPS, fr.columns(g), dispatch)
+    lat = F.ref.rows(tree_base(name), T, dispatch)[0]
+    assert not codes and not np.isnan(out).any() and not np.isnan(lat).any()
+    out.setflags(write=False)
+    lat.setflags(write=False)
+    return out, lat
+
+
+def run_folds(route, name, dispatch, seed):
+    import torch
+    g = tree_graph(name)
+    S, idx = repeated(tree_base(name), NS_TREE, seed)
+    T = np.arange(g.n, dtype=np.int32)
+    eng = route.RouteEngine(g)
+    d = torch.device("cuda", 0)
+    out = torch.full((4, len(S), g.n), -7.0, dtype=torch.float64, device=d)
+    eng.fold_async(dev(S), dev(T), FOLD_OPS, dev(fr.columns(g)), out, dispatch=dispatch)
+    assert sync_code(route, eng) == route.OK
+    want, lat = fold_rows(name, dispatch)
+    assert np.array_equal(out.cpu().numpy(), want[:, idx])
+    one = torch.full((1, len(S), g.n), -7.0, dtype=torch.float64, device=d)
+    eng.fold_async(dev(S), dev(T), [fr.SUM], dev(np.asarray(g.latency, np.float64)), one, dispatch=dispatch)
+    assert sync_code(route, eng) == route.OK
+    assert np.array_equal(one.cpu().numpy()[0], lat[idx])     # the sum of the latencies is the rows' lat
+    return eng
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("name", ["ba400", "ties"])
+def test_folds(route, monkeypatch, name, lds):
+    """Four folds in one call: the carried folds of a workgroup's first source must not reach its second."""
+    form(monkeypatch, name, "fold", lds, NS_TREE)
+    run_folds(route, name, False, 21)
+
+
+# -- link outages
+
+@functools.lru_cache(maxsize=None)
+def outage_ref_of(name):
+    return orf.OutageRef(tree_graph(name))
+
+
+def tree_edge(name, b, where):
+    """The parent edge of a vertex of base source b's tree: where = 0.0 the nearest level .. 1.0 the deepest."""
+    _, pe, _, _, order = outage_ref_of(name)._tree(int(tree_base(name)[b]))
+    return int(pe[order[int(where * (len(order) - 1))]])
+
+
+def run_outage(route, name, S, W, scn, want, rows):
+    """outage_async over canary-filled outputs; want: the reference's Result, whose latencies are
+    (scenarios, base sources x n) when rows (the base index of every source row) is given."""
+    import torch
+    g = tree_graph(name)
+    T = np.arange(g.n, dtype=np.int32)
+    off, edge = orf.pack([sorted(f) for f in scn])
+    eng = route.RouteEngine(g)
+    d = torch.device("cuda", 0)
+    st = torch.full((len(scn), 3), 7, dtype=torch.int64, device=d)
+    mx = torch.full((len(scn),), 7.25, dtype=torch.float64, device=d)
+    nl = torch.full((len(scn), len(S), g.n), 7.25, dtype=torch.float64, device=d)
+    un = torch.full((1,), 7, dtype=torch.int64, device=d)
+    eng.outage_async(dev(S), dev(T), dev(W), dev(off), dev(edge), st, mx, nl, un)
+    assert sync_code(route, eng) == route.OK
+    assert want.codes == frozenset({0}) and want.unrouted == 0 == int(u64(un)[0])
+    assert np.array_equal(u64(st), want.stats), (u64(st).tolist(), want.stats.tolist())
+    assert np.array_equal(mx.cpu().numpy(), want.max_add)
+    wl = want.lat.reshape(len(scn), -1, g.n)
+    assert not np.isnan(wl).any()
+    assert np.array_equal(nl.cpu().numpy(), wl if rows is None else wl[:, rows])
+
+
+@functools.lru_cache(maxsize=None)
+def outage_sources_case(name):
+    """1031 source rows x 3 scenarios.  lat: OutageRef.repair of the base sources, gathered by the
+    test; stats: the u64 sums over all 1031 rows, which are linear in the weights modulo 2^64, so
+    the same repair with every base source's rows added up gives them (max_add takes no weights,
+    and every base source occurs)."""
+    g = tree_graph(name)
+    base = tree_base(name)
+    S, idx = repeated(base, NS_TREE, 22)
+    W = load_weights(len(S), g.n, 23)
+    a, b, c = tree_edge(name, 0, 0.0), tree_edge(name, 17, 0.5), tree_edge(name, 40, 1.0)
+    scn = [[a], sorted({b, c}), [c]]
+    want = outage_ref_of(name).repair(*orf.block_entries(base, np.arange(g.n), summed(W, idx, len(base))), scn)
+    assert len(np.unique(idx)) == len(base)
+    assert want.stats[:, orf.HIT].all() and want.stats[:, orf.SLOWER].any() and want.max_add.max() > 0
+    return S, idx, W, scn, want
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("name", ["ba400", "ties"])
+def test_outage_sources(route, monkeypatch, name, lds):
+    """One slab of three scenarios per source: every second trip of a workgroup is a new source,
+    whose level order is rebuilt over marks that the first one must have left clean."""
+    S, idx, W, scn, want = outage_sources_case(name)
+    assert orf.units(len(S), len(scn)) == (3, 1, NS_TREE)
+    form(monkeypatch, name, "outage", lds, orf.units(len(S), len(scn))[2])
+    run_outage(route, name, S, W, scn, want, idx)
+
+
+@functools.lru_cache(maxsize=None)
+def outage_slabs_case(name):
+    """7 sources x 147 single-edge scenarios, the edges spread over the tree of the first source."""
+    g = tree_graph(name)
+    S = tree_base(name)[:7]
+    _, pe, _, _, order = outage_ref_of(name)._tree(int(S[0]))
+    edges = sorted({int(pe[v]) for v in order})
+    scn = [[e] for e in edges[:: len(edges) // 147][:147]]
+    W = load_weights(len(S), g.n, 24)
+    want = outage_ref_of(name).repair(*orf.block_entries(S, np.arange(g.n), W), scn)
+    assert len(scn) == 147 and np.count_nonzero(want.stats[:, orf.HIT]) > 147 // 2 and want.stats[:, orf.SLOWER].any()
+    return S, W, scn, want
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("name", ["ba400", "ties"])
+def test_outage_slabs(route, monkeypatch, name, lds):
+    """147 slabs of one scenario per source: a workgroup's second unit is another source's slab
+    (units 1024 .. 1028 are the last source's, unit b the first's)."""
+    S, W, scn, want = outage_slabs_case(name)
+    assert orf.units(len(S), len(scn)) == (1, 147, 1029)
+    form(monkeypatch, name, "outage", lds, orf.units(len(S), len(scn))[2])
+    run_outage(route, name, S, W, scn, want, None)
+
+
+# -- ECMP loads
+
+@functools.lru_cache(maxsize=None)
+def ecmp_case(name, dispatch=False):
+    """(S, idx, W, EcmpRef.rows of the whole list in f64, its derived tolerance)."""
+    g = tree_graph(name)
+    S, idx = repeated(tree_base(name), NS_TREE, 25)
+    W = np.random.default_rng(26).integers(0, 1 << 20, size=(len(S), g.n)).astype(np.uint64)
+    W[len(S) // 3] = 0
+    E = er.EcmpRef(g)
+    want = E.rows(S, np.arange(g.n), W, dispatch)
+    assert want[2] == 0 and not want[3]
+    return S, idx, W, want, E.tol(S, dispatch=dispatch)
+
+
+def run_ecmp(route, name, dispatch):
+    import torch
+    g = tree_graph(name)
+    S, idx, W, want, rtol = ecmp_case(name, dispatch)
+    T = np.arange(g.n, dtype=np.int32)
+    eng = route.RouteEngine(g)
+    d = torch.device("cuda", 0)
+    de = torch.full((g.m,), 9.5, dtype=torch.float64, device=d)
+    dt = torch.full((g.n,), 9.5, dtype=torch.float64, device=d)
+    du = torch.full((1,), 9, dtype=torch.int64, device=d)
+    eng.ecmp_loads_async(dev(S), dev(T), dev(W), de, dt, du, dispatch=dispatch)
+    assert sync_code(route, eng) == route.OK and int(u64(du)[0]) == 0
+    assert er.close(de.cpu().numpy(), want[0], rtol) and er.close(dt.cpu().numpy(), want[1], rtol)
+    return eng, S, idx, W
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("name", ["ba400", "ties"])
+def test_ecmp(route, monkeypatch, name, lds):
+    """Against EcmpRef over the whole list within its derived tolerance; then with the weight of
+    every tied entry set to zero, where the ECMP loads are shd_route_loads' converted to f64,
+    whole numbers below 2^53 that add exactly in any order."""
+    import torch
+    form(monkeypatch, name, "ecmp", lds, NS_TREE)
+    eng, S, idx, W = run_ecmp(route, name, False)
+    g = tree_graph(name)
+    T = np.arange(g.n, dtype=np.int32)
+    one = ties_rows(name)[0][idx] == 1
+    if name == "ties":
+        assert np.count_nonzero(~one) > len(S) and W[~one].any()      # tied entries took part in the first run
+    W1 = np.where(one, W, np.uint64(0)).astype(np.uint64)
+    d = torch.device("cuda", 0)
+    de = torch.full((g.m,), 9.5, dtype=torch.float64, device=d)
+    dt = torch.full((g.n,), 9.5, dtype=torch.float64, device=d)
+    le = torch.full((g.m,), 9, dtype=torch.int64, device=d)
+    lt = torch.full((g.n,), 9, dtype=torch.int64, device=d)
+    du = [torch.full((1,), 9, dtype=torch.int64, device=d) for _ in range(2)]
+    eng.ecmp_loads_async(dev(S), dev(T), dev(W1), de, dt, du[0], dispatch=False)
+    eng.loads_async(dev(S), dev(T), dev(W1), le, lt, du[1], dispatch=False)
+    assert sync_code(route, eng) == route.OK and int(u64(du[0])[0]) == int(u64(du[1])[0]) == 0
+    assert 0 < int(u64(le).max()) < 2 ** 53 and u64(lt).any()
+    assert np.array_equal(de.cpu().numpy(), u64(le).astype(np.float64))
+    assert np.array_equal(dt.cpu().numpy(), u64(lt).astype(np.float64))
+
+
+# -- link loss
+
+@functools.lru_cache(maxsize=None)
+def loss_case(name, dispatch=False):
+    """(S, idx, W1, W2, r1, r2, x1, x2) of a call with the weights W1 and a second one that adds
+    the weights W2 on top.  r1, r2: LossRef.block of the whole list in f64, which counts R and A
+    of either call (r2 starts from r1's outputs: one more addend wherever those are not zero).
+    x1, x2: the exact fractions of either call's own terms.  In exact arithmetic the outputs are
+    linear in the weights as long as no u64 sum wraps, so LossRef.block of the base sources with
+    each one's rows added up is LossRef.block of the whole list, at a twentieth of the cost."""
+    g = tree_graph(name)
+    base = tree_base(name)
+    T = np.arange(g.n, dtype=np.int32)
+    S, idx = repeated(base, NS_TREE, 27)
+    W1 = load_weights(len(S), g.n, 28)
+    W2 = np.random.default_rng(29).integers(0, 1000, size=(len(S), g.n)).astype(np.uint64)
+    L = lr.LossRef(g)
+    r1 = L.block(S, T, W1, dispatch)
+    r2 = L.block(S, T, W2, dispatch, init=r1.arrays())
+    assert int(W1.sum(dtype=np.uint64)) + int(W2.sum(dtype=np.uint64)) < 2 ** 63            # nothing wraps
+    x1 = L.block(base, T, summed(W1, idx, len(base)), dispatch, exact=True)
+    x2 = L.block(base, T, summed(W2, idx, len(base)), dispatch, exact=True)
+    for r, x in ((r1, x1), (r2, x2)):
+        assert (r.R, r.unrouted, r.codes, r.routed) == (x.R, 0, set(), x.routed) and r.A > 2
+    return S, idx, W1, W2, r1, r2, x1, x2
+
+
+def loss_outs(g, d):
+    import torch
+    return ([torch.full((k,), 7.25, dtype=torch.float64, device=d) for k in (g.m, g.m, g.n, g.n)]
+            + [torch.full((1,), 7, dtype=torch.int64, device=d)])
+
+
+def run_loss(route, name, dispatch):
+    import torch
+    from fractions import Fraction
+    g = tree_graph(name)
+    S, idx, W1, W2, r1, r2, x1, x2 = loss_case(name, dispatch)
+    T = np.arange(g.n, dtype=np.int32)
+    eng = route.RouteEngine(g)
+    outs = loss_outs(g, torch.device("cuda", 0))
+    eng.loss_async(dev(S), dev(T), dev(W1), *outs, dispatch=dispatch)
+    assert sync_code(route, eng) == route.OK and int(u64(outs[4])[0]) == 0
+    got1 = [o.cpu().numpy() for o in outs[:4]]
+    for k in range(4):
+        assert lr.close(got1[k], x1.outs()[k], r1.R, r1.A), (lr.NAMES[k], r1.R, r1.A)
+    assert got1[0].any() and got1[1].any() and got1[3].any()
+    # a second call adds other weights on top of what the first one left
+    eng.loss_async(dev(S), dev(T), dev(W2), *outs, dispatch=dispatch, add=True)
+    assert sync_code(route, eng) == route.OK and int(u64(outs[4])[0]) == 0
+    for k in range(4):
+        want = [Fraction(a) + b for a, b in zip(got1[k].tolist(), x2.outs()[k])]
+        assert lr.close(outs[k].cpu().numpy(), want, r2.R, r2.A), (lr.NAMES[k], r2.R, r2.A)
+    return S, W1
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("name", ["ba400", "ties"])
+def test_loss(route, monkeypatch, name, lds):
+    """All four outputs within (R + 4 + A) * 2^-52 of the exact fractions, a second call that
+    adds, and on a copy of the graph without any loss edge_reach equal to shd_route_loads' edge
+    load converted to f64, exactly, with nothing dropped."""
+    import dataclasses
+    import torch
+    form(monkeypatch, name, "loss", lds, NS_TREE)
+    S, W = run_loss(route, name, False)
+    g = tree_graph(name)
+    g0 = dataclasses.replace(g, packetloss=np.zeros(g.m), vertex_packetloss=None, name=g.name + "_zero")
+    T = np.arange(g.n, dtype=np.int32)
+    eng = route.RouteEngine(g0)
+    d = torch.device("cuda", 0)
+    outs = loss_outs(g0, d)
+    le = torch.full((g.m,), 9, dtype=torch.int64, device=d)
+    eng.loss_async(dev(S), dev(T), dev(W), *outs, dispatch=False)
+    eng.loads_async(dev(S), dev(T), dev(W), le, None, None, dispatch=False)
+    assert sync_code(route, eng) == route.OK and int(u64(outs[4])[0]) == 0
+    assert 2 ** 40 < int(u64(le).max()) < 2 ** 53
+    assert np.array_equal(outs[0].cpu().numpy(), u64(le).astype(np.float64))
+    assert not outs[1].cpu().numpy().any() and not outs[2].cpu().numpy().any()
+    assert float(outs[3].cpu().numpy().sum()) == float(int(W.sum(dtype=np.uint64)))
+
+
+# -- dispatch: a complete graph (no rows launch, no sweep, no state) and a prefer-direct one
+
+RUN = {"ecmp": lambda route, name: run_ecmp(route, name, True),
+       "fold": lambda route, name: run_folds(route, name, True, 30),
+       "loss": lambda route, name: run_loss(route, name, True)}
+
+
+@pytest.mark.parametrize("family", ["ecmp", "fold", "loss"])
+@pytest.mark.parametrize("name", ["k24", "ba80_prefer"])
+def test_dispatch(route, name, family):
+    """1031 source rows under SHD_ROUTE_DISPATCH.  k24 is complete: mode 2 of state_form, a grid
+    of min(k, 1024) whose workgroups `continue` past the sweep after a lone barrier, also for
+    their second source.  ba80_prefer mixes direct and tree entries in every row, in the LDS form."""
+    from tests.multi_ref import Ref
+    g = tree_graph(name)
+    R = Ref(g)
+    assert NS_TREE > TREE_LDS_CAP and NS_TREE <= (1 << 30) // (16 * g.n) and FAMILY_REF[family].fits_lds(g.n)
+    if name == "k24":
+        assert R.complete and len(tree_base(name)) == g.n
+    else:
+        direct = sum(R.is_direct(int(s), t, True) for s in tree_base(name)[:8] for t in range(g.n) if t != s)
+        assert g.prefer_direct and not R.complete and 8 < direct < 4 * g.n
+    RUN[family](route, name)
+
+
+# -- the pair forms: pairs are grouped by distinct source, so the cap takes 1,056 vertices
+
+GRID = "grid"
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pairs():
+    """Every vertex of the 1,056-vertex lattice as a source with three random targets (vertex 0's
+    first is its neighbour 1, whose one shortest path is their edge), shuffled, weighted."""
+    g = tout.graph(GRID)
+    rng = np.random.default_rng(31)
+    ps = np.repeat(np.arange(g.n, dtype=np.int32), 3)
+    pt = ((ps + rng.integers(1, g.n, size=len(ps))) % g.n).astype(np.int32)     # no self pair: a third of the
+    pt[0] = 1                                                                    # vertices has no self-loop
+    pw = rng.integers(0, 1000, size=len(ps)).astype(np.uint64)
+    pw[0], pw[7] = np.uint64(5), np.uint64(2 ** 40 + 3)
+    k = rng.permutation(len(ps))
+    return ps[k], pt[k], pw[k]
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pair_ref(family):
+    g = tout.graph(GRID)
+    ps, pt, pw = grid_pairs()
+    if family == "fold":
+        return fr.FoldRef(g).pairs(ps, pt, FOLD_OPS, fr.columns(g))
+    if family == "ecmp":
+        E = er.EcmpRef(g)
+        mult = int(np.unique(ps.astype(np.int64) * g.n + pt, return_counts=True)[1].max())
+        return E.pairs(ps, pt, pw), E.tol(np.unique(ps), mult=mult)
+    if family == "loss":
+        L = lr.LossRef(g)
+        return L.pairs(ps, pt, pw), L.pairs(ps, pt, pw, exact=True)
+    O = tout.ref(GRID)
+    es = O.ref.path(0, g.n - 1)[1]
+    scn = [[int(O.ref.path(0, 1)[1][0])], sorted([int(es[1]), int(es[-2])])]
+    return scn, O.repair(ps, pt, pw, scn)
+
+
+@pytest.mark.parametrize("family", ["ecmp", "fold", "loss", "outage"])
+def test_pair_forms(route, family):
+    """shd_route_pair_{ecmp_loads,fold,loss,outage} over 1,056 distinct sources in one chunk, all
+    in the LDS form: workgroups 0 .. 31 take a second source."""
+    g = tout.graph(GRID)
+    ps, pt, pw = grid_pairs()
+    k = len(np.unique(ps))
+    assert k == g.n == 1056 > TREE_LDS_CAP and k <= (1 << 30) // (16 * g.n)
+    assert g.n < min(m.lds_max_n() for m in FAMILY_REF.values()) and g.vertex_packetloss is None
+    eng = route.RouteEngine(g)
+    want = grid_pair_ref(family)
+    if family == "fold":
+        assert not want[1] and not np.isnan(want[0]).any()
+        got = eng.pair_fold(ps, pt, FOLD_OPS, fr.columns(g), dispatch=False)
+        assert np.array_equal(got, want[0])
+    elif family == "ecmp":
+        (we, wt, wu, codes), rtol = want
+        ge, gt, gu = eng.pair_ecmp_loads(ps, pt, pw, dispatch=False)
+        assert not codes and gu == wu == 0
+        assert er.close(ge, we, rtol) and er.close(gt, wt, rtol)
+    elif family == "loss":
+        f64, exact = want
+        got = eng.pair_loss(ps, pt, pw, dispatch=False)
+        assert (exact.R, exact.A, exact.unrouted, exact.codes) == (f64.R, f64.A, 0, set()) and got[4] == 0
+        for j in range(4):
+            assert lr.close(got[j], exact.outs()[j], exact.R, exact.A), (lr.NAMES[j], exact.R, exact.A)
+    else:
+        scn, w = want
+        assert w.codes == frozenset({0}) and w.stats[:, orf.HIT].all() and w.stats[:, orf.SLOWER].any()
+        st, mx, nl, un = eng.pair_outage(ps, pt, scn, pw, lat=True)
+        assert un == w.unrouted == 0 and np.array_equal(st, w.stats) and np.array_equal(mx, w.max_add)
+        assert np.array_equal(nl, w.lat, equal_nan=True) and not np.isnan(w.lat).any()

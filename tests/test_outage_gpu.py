@@ -515,3 +515,20 @@ def test_front_end_dispatching_cache_is_unsupported(topo, route, name):
     with pytest.raises(RuntimeError, match=r"\(-6\)"):
         t.link_outage([[0]])
     t.close()
+
+
+# ---- two live contexts ------------------------------------------------------------------------------------
+
+def test_two_live_contexts(route):
+    """A context at the LDS limit and one of 64 vertices, both in the LDS form, their calls
+    alternated: the dynamic-LDS limit of the kernel is raised once per context, each launch takes
+    its own context's state size, columns and scratch, and each still equals its reference."""
+    big, small = f"sized{orf.lds_max_n()}", "ba64_ties"
+    gb, gs = tout.graph(big), tout.graph(small)
+    assert orf.fits_lds(gb.n) and orf.fits_lds(gs.n) and orf.layout_total(gb.n) > 100 * orf.layout_total(gs.n)
+    eb = route.RouteEngine(gb)
+    es = route.RouteEngine(gs)
+    for _ in range(2):
+        _, _, wb = check_block(route, big, eb)
+        _, _, ws = check_block(route, small, es)
+    assert wb.stats[:, orf.HIT].any() and ws.stats[:, orf.HIT].any()
