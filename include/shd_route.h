@@ -15,8 +15,9 @@
  * rows launch inside and fall under the same rule, and so do the tie envelope calls
  * (shd_route_ties*), the ECMP link loads calls (shd_route_ecmp_loads*,
  * shd_route_pair_ecmp_loads), the path fold calls (shd_route_fold*, shd_route_pair_fold),
- * the link loss calls (shd_route_loss*, shd_route_pair_loss) and the link outage calls
- * (shd_route_outage*, shd_route_pair_outage).
+ * the link loss calls (shd_route_loss*, shd_route_pair_loss), the link outage calls
+ * (shd_route_outage*, shd_route_pair_outage) and the link repricing calls (shd_route_reprice*,
+ * shd_route_pair_reprice).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -42,15 +43,17 @@
  *                  ties and ECMP loads calls also their per-arc reliabilities and out-CSR, the
  *                  ECMP loads calls the out-arcs' edge ids; the loss calls also their per-edge
  *                  and per-vertex loss columns, the outage calls the edges' ends and latencies
- *                  and the self-loop lists); all once per context
+ *                  and the self-loop lists, the repricing calls what the outage and the ECMP
+ *                  loads calls build); all once per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
  *                  the hops, loads, folds, ties and ECMP loads calls when their source chunk
- *                  grows (the loss and outage calls follow the loads calls),
+ *                  grows (the loss, outage and repricing calls follow the loads calls),
  *                  shd_route_loads_async, shd_route_fold_async, shd_route_ties_async,
- *                  shd_route_ecmp_loads_async, shd_route_loss_async and shd_route_outage_async
- *                  in their HBM forms when the slices grow (those synchronise the stream)
+ *                  shd_route_ecmp_loads_async, shd_route_loss_async, shd_route_outage_async and
+ *                  shd_route_reprice_async in their HBM forms when the slices grow (those
+ *                  synchronise the stream)
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -88,6 +91,9 @@
  *   shd_route_loss, shd_route_pair_loss <- (no reference equivalent; the reference drops a
  *                         packet with one end-to-end coin flip on the Path's reliability and
  *                         cannot say on which link or router it was lost)
+ *   shd_route_outage, shd_route_pair_outage, shd_route_reprice, shd_route_pair_reprice <- (no
+ *                         reference equivalent; what-if scenarios that remove links or change
+ *                         their latencies)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -609,6 +615,88 @@ int shd_route_pair_outage(shd_route_t* ctx, const int32_t* pair_src, const int32
                           const uint64_t* pair_wt, int64_t npairs, uint32_t flags, const int64_t* scn_off,
                           const int32_t* scn_edge, int32_t nscn, uint64_t* stats_out, double* max_add_out,
                           double* lat_out, uint64_t* unrouted_out);
+
+/* ---- link repricing: what the entries gain or lose when a set of edges gets other latencies ----
+ * No reference equivalent: a user of Shadow 1.14 loads another topology.
+ * Scenario k is the list of pairs (scn_edge[x], scn_lat[x]) for x in scn_off[k] .. scn_off[k+1));
+ * G_k is the context's graph with those edges' latencies replaced: edge order, ends, losses and
+ * everything else stay as they are.  An undirected edge changes both arcs, a directed edge its
+ * one arc, a self-loop the self entry only.  A new latency must be finite and > 0, anything else
+ * is SHD_ROUTE_EINVAL; removal stays with the outage calls.  An id repeated within one scenario
+ * is SHD_ROUTE_EINVAL (the async form asks for strictly ascending ids); a new latency equal to
+ * the old one is allowed.
+ *   Absorbed latencies follow the rule at shd_graph_t: with lo the minimum and hi the maximum
+ * over the graph's latencies on edges that are no self-loops and every new latency of the call
+ * put on such an edge, lo <= (n_vertices - 1) * hi * 2^-52 makes the whole call
+ * SHD_ROUTE_EUNSUPPORTED with nothing computed (the host forms refuse before they launch, the
+ * async form raises it on the error word from its check kernel).  The rule is sufficient for
+ * every G_k at once and therefore conservative: it may refuse a call none of whose scenarios,
+ * taken alone, would be refused as a graph.
+ *   Every entry (src[i], tgt[j], weight) is judged without dispatch, as for the outage calls:
+ * flags must be 0, SHD_ROUTE_DISPATCH or any other bit is SHD_ROUTE_EINVAL.
+ *   old = the entry in G.  An entry that fails in G (SHD_ROUTE_ENOEDGE, SHD_ROUTE_EUNREACH) raises
+ * its code, adds its weight to *unrouted once (not once per scenario) and takes part in no
+ * scenario.
+ *   new = the entry of a context created from G_k: for t != s the shortest latency in G_k (the
+ * f64 left fold from the source), for t == s the latency in G_k of the lowest-id self-loop of s.
+ * Connectivity does not change, so nothing is ever cut.
+ *   Per scenario, stats[k*SHD_ROUTE_REPRICE_NSTAT + ...] in u64 adds, exact mod 2^64 and
+ * independent of order:
+ *     SHD_ROUTE_REPRICE_HIT     the weight of the entries whose old route, the one shd_route_paths
+ *                               reports, uses a listed edge (for a self entry: the lowest self-loop);
+ *     SHD_ROUTE_REPRICE_SLOWER  the weight of the entries with new > old;
+ *     SHD_ROUTE_REPRICE_FASTER  the weight of the entries with new < old;
+ * max_add[k] = the largest new - old over the slower entries and max_gain[k] = the largest
+ * old - new over the faster ones (one f64 subtraction per entry, 0.0 without any entry of that
+ * kind, a u64 maximum on the bits); min_new[k] = the smallest new latency over the entries that
+ * route in G (a u64 minimum on the bits, +inf without any such entry): the runahead window a
+ * simulation of G_k would get from these entries.  lat[(k*ns + i)*ld + j], if asked for, is the
+ * new latency, NaN where the entry failed in G; it is bit-equal to lat of shd_route_rows with
+ * flags 0 on a context created from G_k.  An entry that is hit but keeps its latency counts in
+ * hit only.  Reliability and hops of the new routes are not computed.
+ *   nscn == 0 writes only *unrouted; an empty scenario gives zero stats and the old latencies,
+ * with min_new the old minimum.
+ *   The calls run a rows launch inside (the "one rows launch at a time" rule covers them) and
+ * follow the outage calls' scratch and work units.  A unit holds the source's old row as its
+ * current distances, finds the scenarios that reprice a parent arc or the source's lowest
+ * self-loop or lower an edge below the distance gap of its ends (every other scenario leaves the
+ * row as it is), marks the subtrees below the listed tree arcs and rebuilds them as an outage
+ * does, a listed arc taken at its new latency, then pushes what fell along the out-arcs, round by
+ * round, until nothing falls, and puts the touched vertices back.  The state
+ * (21.25 bytes per vertex while n <= 65535, 29.25 above) lives in LDS up to 7,456 vertices or, on
+ * larger graphs and with SHD_ROUTE_REPRICE_LDS=0, in HBM slices of 16 to 512 workgroup slots
+ * within a quarter of SHD_ROUTE_HOPS_SCRATCH, regrown (which synchronises the stream) when a
+ * launch needs more.  First use blocks for what the outage and the ECMP loads calls build, once
+ * per context.  Diagnostic rate: every call runs the sources' SSSP. */
+#define SHD_ROUTE_REPRICE_HIT 0
+#define SHD_ROUTE_REPRICE_SLOWER 1
+#define SHD_ROUTE_REPRICE_FASTER 2
+#define SHD_ROUTE_REPRICE_NSTAT 3
+/* Device pointers, as shd_route_outage_async, with d_scn_lat beside d_scn_edge (each scenario
+ * strictly ascending in its ids); d_max_gain[nscn] and d_min_new[nscn] beside d_max_add; any
+ * output may be NULL.  A validation kernel raises SHD_ROUTE_EINVAL on the error word for an
+ * offset, range, order or latency violation and SHD_ROUTE_EUNSUPPORTED for the absorbed-latency
+ * rule (the outputs are then undefined); the main kernel indexes no memory with an unchecked
+ * id. */
+int shd_route_reprice_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                            int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                            const int64_t* d_scn_off, const int32_t* d_scn_edge, const double* d_scn_lat,
+                            int32_t nscn, uint64_t* d_stats, double* d_max_add, double* d_max_gain,
+                            double* d_min_new, double* d_lat, uint64_t* d_unrouted, void* stream);
+/* Same with host pointers (row stride nt); blocks.  Scenario ids in any order: each scenario is
+ * sorted by id inside.  An id outside [0, n_edges), a repeated id, a bad latency or a vertex out
+ * of range is SHD_ROUTE_EINVAL for the whole call, nothing written. */
+int shd_route_reprice(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                      uint32_t flags, const uint64_t* wt, const int64_t* scn_off, const int32_t* scn_edge,
+                      const double* scn_lat, int32_t nscn, uint64_t* stats_out, double* max_add_out,
+                      double* max_gain_out, double* min_new_out, double* lat_out, uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[p], pair_tgt[p], pair_wt[p]) in any order (pair_wt NULL =
+ * 1 each); lat_out[k*npairs + p] in the caller's pair order.  Host pointers; blocks. */
+int shd_route_pair_reprice(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                           const uint64_t* pair_wt, int64_t npairs, uint32_t flags, const int64_t* scn_off,
+                           const int32_t* scn_edge, const double* scn_lat, int32_t nscn, uint64_t* stats_out,
+                           double* max_add_out, double* max_gain_out, double* min_new_out, double* lat_out,
+                           uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

@@ -200,6 +200,21 @@ int shd_topology_link_loss(shd_topology_t* top, double* edge_reach, double* edge
  * nothing cached, every total zero before the first fill; each output may be NULL. */
 int shd_topology_link_outage(shd_topology_t* top, const int64_t* scn_off, const int32_t* scn_edge, int32_t nscn,
                              uint64_t* stats, double* max_add, uint64_t* unrouted);
+/* What the same pairs and counters gain or lose when links get other latencies: scenario k puts
+ * scn_lat[x] on the edge id scn_edge[x] for x in scn_off[k] .. scn_off[k+1]), in any order
+ * (shd_route_pair_reprice in shd_route.h).  stats[nscn * SHD_ROUTE_REPRICE_NSTAT] = per scenario
+ * the packets whose route used a repriced link, those that get slower and those that get faster;
+ * max_add[nscn] and max_gain[nscn] = the largest added and the largest gained latency;
+ * min_new[nscn] = the smallest new latency over the counted pairs, the runahead window they would
+ * give (+inf without a counted pair); *unrouted = the packets of pairs without a route in the
+ * whole graph.  Tree routes only: a topology whose cache dispatches (a complete graph, or
+ * prefer-direct) returns SHD_ROUTE_EUNSUPPORTED.  An id outside [0, n_edges), an id repeated in a
+ * scenario or a latency that is not finite and > 0 is SHD_ROUTE_EINVAL, nothing written.  Same
+ * rules: engine 0 under the lock, nothing cached, stats and maxima zero and min_new +inf before
+ * the first fill; each output may be NULL. */
+int shd_topology_link_reprice(shd_topology_t* top, const int64_t* scn_off, const int32_t* scn_edge,
+                              const double* scn_lat, int32_t nscn, uint64_t* stats, double* max_add,
+                              double* max_gain, double* min_new, uint64_t* unrouted);
 /* ---- path folds: a per-link quantity along the stored Paths ---------------------------------
  * No reference equivalent (shd_route_pair_fold in shd_route.h).  Like the route calls above
  * these run on engine 0 under the topology lock, compute on demand (diagnostic rate), cache

@@ -31,6 +31,7 @@
 #include "path_fold.hpp"
 #include "link_loss.hpp"
 #include "link_outage.hpp"
+#include "link_reprice.hpp"
 #include "fill_sched.hpp"
 #include "select.hpp"
 #include "path_host.hpp"

@@ -98,7 +98,8 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 
 // ---- the form of a per-source state kernel ----
 // hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, loss_tree_kernel, ties_dag_kernel,
-// ecmp_dag_kernel and outage_repair_kernel (k = its work units) keep one source's state per workgroup:
+// ecmp_dag_kernel, outage_repair_kernel and reprice_kernel (k = their work units) keep one source's state per
+// workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
 // else u16 (n <= 65535) or u32 state in HBM slices, one per resident workgroup.
@@ -168,6 +169,13 @@ struct PathDev {
     int* ou_ea = nullptr; int* ou_eb = nullptr; double* ou_lat = nullptr;
     int* ou_srow = nullptr; int* ou_seid = nullptr;
     PathSlices ou_ws;
+    // link repricing: the smallest and the largest latency over the edges that are no
+    // self-loops (rp_lo > rp_hi: none), the two words its check kernels reduce into, set at the
+    // first repricing call; and the HBM slices
+    int rp_ready = 0;
+    double rp_lo = 0.0, rp_hi = 0.0;
+    unsigned long long* rp_lohi = nullptr;
+    PathSlices rp_ws;
 };
 
 }  // namespace shd

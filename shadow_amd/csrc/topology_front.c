@@ -891,6 +891,46 @@ int shd_topology_link_outage(shd_topology_t* t, const int64_t* scn_off, const in
     return rc;
 }
 
+/* ---- link repricing over the stored Paths (shd_route_pair_reprice on engine 0, nothing cached) ---- */
+
+int shd_topology_link_reprice(shd_topology_t* t, const int64_t* scn_off, const int32_t* scn_edge,
+                              const double* scn_lat, int32_t nscn, uint64_t* stats, double* max_add,
+                              double* max_gain, double* min_new, uint64_t* unrouted) {
+    if (!t || nscn < 0 || (nscn && !scn_off)) return SHD_ROUTE_EINVAL;
+    if (t->complete || t->prefer_direct) return SHD_ROUTE_EUNSUPPORTED;  /* the cache dispatches */
+    if (nscn && (scn_off[0] != 0 || (scn_off[nscn] && (!scn_edge || !scn_lat)))) return SHD_ROUTE_EINVAL;
+    for (int32_t k = 0; k < nscn; k++)
+        if (scn_off[k + 1] < scn_off[k]) return SHD_ROUTE_EINVAL;
+    for (int32_t k = 0; k < nscn; k++)
+        for (int64_t x = scn_off[k]; x < scn_off[k + 1]; x++) {
+            if (scn_edge[x] < 0 || scn_edge[x] >= t->g.n_edges || !(scn_lat[x] > 0.0) || isinf(scn_lat[x]))
+                return SHD_ROUTE_EINVAL;
+            for (int64_t y = scn_off[k]; y < x; y++)
+                if (scn_edge[y] == scn_edge[x]) return SHD_ROUTE_EINVAL;
+        }
+    for (int64_t k = 0; k < nscn; k++) {
+        if (stats)
+            for (int q = 0; q < SHD_ROUTE_REPRICE_NSTAT; q++) stats[k * SHD_ROUTE_REPRICE_NSTAT + q] = 0;
+        if (max_add) max_add[k] = 0.0;
+        if (max_gain) max_gain[k] = 0.0;
+        if (min_new) min_new[k] = INFINITY;
+    }
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0;
+    int rc = counted_pairs(t, &ps, &pt, &pw, &np);
+    if (!rc && np) {
+        rc = shd_route_pair_reprice(t->eng[0], ps, pt, pw, (int64_t)np, 0u, scn_off, scn_edge, scn_lat, nscn, stats,
+                                    max_add, max_gain, min_new, NULL, unrouted);
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;  /* as above */
+    }
+    pthread_mutex_unlock(&t->lock);
+    free(ps); free(pt); free(pw);
+    return rc;
+}
+
 /* ---- path folds along the stored Paths (shd_route_pair_fold on engine 0, nothing cached) ---- */
 
 int shd_topology_edge_jitter(shd_topology_t* t, double* out) {

@@ -32,6 +32,7 @@ LOADS_ADD = 0x400  # shd_route.h SHD_ROUTE_LOADS_ADD
 FOLD_SUM, FOLD_MIN, FOLD_MAX, FOLD_PROD = 0, 1, 2, 3  # SHD_ROUTE_FOLD_*
 FOLD_MAX_N = 8
 OUTAGE_HIT, OUTAGE_CUT, OUTAGE_SLOWER, OUTAGE_NSTAT = 0, 1, 2, 3  # SHD_ROUTE_OUTAGE_*
+REPRICE_HIT, REPRICE_SLOWER, REPRICE_FASTER, REPRICE_NSTAT = 0, 1, 2, 3  # SHD_ROUTE_REPRICE_*
 
 
 class RouteError(RuntimeError):
@@ -93,6 +94,7 @@ EXPORTS = (
     "shd_route_fold_async", "shd_route_fold", "shd_route_pair_fold",
     "shd_route_loss_async", "shd_route_loss", "shd_route_pair_loss",
     "shd_route_outage_async", "shd_route_outage", "shd_route_pair_outage",
+    "shd_route_reprice_async", "shd_route_reprice", "shd_route_pair_reprice",
 )
 
 _lib = None
@@ -199,6 +201,12 @@ def load_library():
     L.shd_route_outage.argtypes = [P, P, I32, P, I32, U32, P, P, P, I32, P, P, P, P]
     L.shd_route_pair_outage.restype = C.c_int
     L.shd_route_pair_outage.argtypes = [P, P, P, P, I64, U32, P, P, I32, P, P, P, P]
+    L.shd_route_reprice_async.restype = C.c_int
+    L.shd_route_reprice_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P, I32, P, P, P, P, P, P, P]
+    L.shd_route_reprice.restype = C.c_int
+    L.shd_route_reprice.argtypes = [P, P, I32, P, I32, U32, P, P, P, P, I32, P, P, P, P, P, P]
+    L.shd_route_pair_reprice.restype = C.c_int
+    L.shd_route_pair_reprice.argtypes = [P, P, P, P, I64, U32, P, P, P, I32, P, P, P, P, P, P]
     L.shd_route_fold_async.restype = C.c_int
     L.shd_route_fold_async.argtypes = [P, P, I32, P, I32, I64, U32, P, I32, P, P, I64, P]
     L.shd_route_fold.restype = C.c_int
@@ -232,6 +240,25 @@ def pack_scenarios(scenarios):
             off[1:] = np.cumsum([len(f) for f in lists])
         edge = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, np.int32)
     return off, np.ascontiguousarray(edge)
+
+
+def pack_reprice(scenarios):
+    """(off int64, edge int32, lat float64) of a list of scenarios, each a list of (edge id, new
+    latency) pairs, or of an (off, edge, lat) tuple of arrays."""
+    if isinstance(scenarios, tuple):
+        off = np.ascontiguousarray(scenarios[0], np.int64)
+        edge = np.ascontiguousarray(scenarios[1], np.int32).reshape(-1)
+        lat = np.ascontiguousarray(scenarios[2], np.float64).reshape(-1)
+    else:
+        lists = [list(f) for f in scenarios]
+        off = np.zeros(len(lists) + 1, np.int64)
+        if lists:
+            off[1:] = np.cumsum([len(f) for f in lists])
+        edge = np.array([e for f in lists for e, _ in f], np.int32)
+        lat = np.array([w for f in lists for _, w in f], np.float64)
+    if len(edge) != len(lat):
+        raise ValueError("one new latency per listed edge id")
+    return off, edge, lat
 
 
 def _check(rc, what):
@@ -582,6 +609,64 @@ class RouteEngine:
         _check(rc, "shd_route_pair_outage")
         return res
 
+    def _reprice_out(self, nscn, entries, lat, out):
+        if out is not None:
+            return out
+        return (np.zeros((nscn, REPRICE_NSTAT), np.uint64), np.zeros(nscn, np.float64), np.zeros(nscn, np.float64),
+                np.full(nscn, np.inf), np.full((nscn, *entries), np.nan) if lat else None, np.zeros(1, np.uint64))
+
+    def reprice(self, sources, targets, scenarios, weights=None, lat: bool = False, out=None):
+        """shd_route_reprice: (stats, max_add, max_gain, min_new, lat, unrouted) of the (source,
+        target) block under every scenario, each a list of (edge id, new latency) pairs: scenarios
+        is a list of such lists or an (off, edge, lat) tuple of arrays.  stats is uint64
+        (scenarios, REPRICE_NSTAT) with the columns REPRICE_HIT, REPRICE_SLOWER and REPRICE_FASTER;
+        max_add, max_gain and min_new (the smallest new latency, +inf without a routed entry) are
+        float64 per scenario; lat=True also returns the new latencies (scenarios, sources,
+        targets), NaN where the entry fails in the graph itself, else None.  Entries are judged
+        without dispatch.  weights as loads().  out: the six arrays of an earlier call's shapes
+        (unrouted a 1-element uint64 array), any of them None for an output not wanted.  A missing
+        self-loop or an unreachable target raises RouteError; ``err.partial`` then holds the
+        results."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        off, edge, nl = pack_reprice(scenarios)
+        nscn = len(off) - 1
+        st, mx, mg, mn, la, un = self._reprice_out(nscn, (len(s), len(t)), lat, out)
+        rc = load_library().shd_route_reprice(self._h, _p(s), len(s), _p(t), len(t), 0, _p(w), _p(off), _p(edge), _p(nl),
+                                              nscn, _p(st), _p(mx), _p(mg), _p(mn), _p(la), _p(un))
+        res = (st, mx, mg, mn, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_reprice")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_reprice")
+        return res
+
+    def pair_reprice(self, pair_src, pair_tgt, scenarios, pair_wt=None, lat: bool = False, out=None):
+        """shd_route_pair_reprice: as reprice() for a list of (source, target, weight) pairs in any
+        order, repeats adding up (pair_wt None = 1 each); lat is (scenarios, pairs) in the
+        caller's pair order."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        off, edge, nl = pack_reprice(scenarios)
+        nscn = len(off) - 1
+        st, mx, mg, mn, la, un = self._reprice_out(nscn, (len(s),), lat, out)
+        rc = load_library().shd_route_pair_reprice(self._h, _p(s), _p(t), _p(w), len(s), 0, _p(off), _p(edge), _p(nl),
+                                                   nscn, _p(st), _p(mx), _p(mg), _p(mn), _p(la), _p(un))
+        res = (st, mx, mg, mn, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_reprice")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_pair_reprice")
+        return res
+
     def _fold_args(self, ops, values):
         o = np.ascontiguousarray(ops, np.int32).reshape(-1)
         v = np.ascontiguousarray(values, np.float64)
@@ -658,6 +743,21 @@ class RouteEngine:
             self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, int(flags), ptr(d_wt), ptr(d_scn_off), ptr(d_scn_edge), nscn,
             ptr(d_stats), ptr(d_max_add), ptr(d_lat), ptr(d_unrouted), C.c_void_p(stream) if stream else None)
         _check(rc, "shd_route_outage_async")
+
+    def reprice_async(self, d_src, d_tgt, d_wt, d_scn_off, d_scn_edge, d_scn_lat, d_stats, d_max_add, d_max_gain,
+                      d_min_new, d_lat, d_unrouted, stream=None, ld=None, flags=0):
+        """shd_route_reprice_async over device tensors: as outage_async(), with float64 new
+        latencies beside the edge ids (each scenario strictly ascending in its ids) and float64
+        max_gain and min_new (scenarios) beside max_add; any output may be None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        nscn = 0 if d_scn_off is None else int(d_scn_off.numel()) - 1
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_reprice_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, int(flags), ptr(d_wt), ptr(d_scn_off), ptr(d_scn_edge),
+            ptr(d_scn_lat), nscn, ptr(d_stats), ptr(d_max_add), ptr(d_max_gain), ptr(d_min_new), ptr(d_lat),
+            ptr(d_unrouted), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_reprice_async")
 
     def loss_async(self, d_src, d_tgt, d_wt, d_edge_reach, d_edge_drop, d_vertex_drop, d_delivered, d_unrouted,
                    stream=None, dispatch=True, ld=None, add=False):

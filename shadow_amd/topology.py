@@ -32,6 +32,7 @@ EXPORTS = (
     "shd_topology_link_loads", "shd_topology_ecmp_link_loads", "shd_topology_dump_link_loads", "shd_topology_link_line",
     "shd_topology_edge_count", "shd_topology_add_path_packets",
     "shd_topology_edge_jitter", "shd_topology_fold_pairs", "shd_topology_link_loss", "shd_topology_link_outage",
+    "shd_topology_link_reprice",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
@@ -118,6 +119,8 @@ def load_library():
     L.shd_topology_ecmp_link_loads.argtypes = [P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_link_outage.restype = C.c_int
     L.shd_topology_link_outage.argtypes = [P, P, P, C.c_int32, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_link_reprice.restype = C.c_int
+    L.shd_topology_link_reprice.argtypes = [P, P, P, P, C.c_int32, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_link_loss.restype = C.c_int
     L.shd_topology_link_loss.argtypes = [P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_edge_jitter.restype = C.c_int
@@ -442,6 +445,28 @@ class Topology:
         if rc:
             raise RuntimeError(f"link_outage failed ({rc})")
         return st, mx, int(un.value)
+
+    def link_reprice(self, scenarios):
+        """shd_topology_link_reprice: (stats, max_add, max_gain, min_new, unrouted) of the cached
+        Paths' packet counters under every scenario of (edge id, new latency) pairs (a list of
+        such lists, or an (off, edge, lat) tuple): uint64 stats (scenarios, 3) = the packets hit,
+        slower and faster, float64 max_add, max_gain and min_new per scenario, an exact integer
+        unrouted.  Raises RuntimeError with SHD_ROUTE_EUNSUPPORTED (-6) for a topology whose cache
+        dispatches (a complete graph, or prefer-direct)."""
+        from .route import pack_reprice
+        L = load_library()
+        off, edge, nl = pack_reprice(scenarios)
+        nscn = len(off) - 1
+        st = np.zeros((nscn, 3), np.uint64)
+        mx, mg, mn = np.zeros(nscn, np.float64), np.zeros(nscn, np.float64), np.full(nscn, np.inf)
+        un = C.c_uint64()
+        vp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+        rc = L.shd_topology_link_reprice(self._h, C.c_void_p(off.ctypes.data), vp(edge), vp(nl), nscn,
+                                         C.c_void_p(st.ctypes.data), C.c_void_p(mx.ctypes.data),
+                                         C.c_void_p(mg.ctypes.data), C.c_void_p(mn.ctypes.data), C.byref(un))
+        if rc:
+            raise RuntimeError(f"link_reprice failed ({rc})")
+        return st, mx, mg, mn, int(un.value)
 
     def edge_jitter(self):
         """shd_topology_edge_jitter: the graphml's jitter edge attribute per edge id (NaN where
