@@ -16,8 +16,8 @@
  * (shd_route_ties*), the ECMP link loads calls (shd_route_ecmp_loads*,
  * shd_route_pair_ecmp_loads), the path fold calls (shd_route_fold*, shd_route_pair_fold),
  * the link loss calls (shd_route_loss*, shd_route_pair_loss), the link outage calls
- * (shd_route_outage*, shd_route_pair_outage) and the link repricing calls (shd_route_reprice*,
- * shd_route_pair_reprice).
+ * (shd_route_outage*, shd_route_pair_outage), the link repricing calls (shd_route_reprice*,
+ * shd_route_pair_reprice) and the link edit calls (shd_route_edit*, shd_route_pair_edit).
  *
  * Several contexts may be alive in one process, on one device or on several, each used as
  * above; creating, using and destroying one never changes what another computes.  (A context
@@ -44,7 +44,8 @@
  *                  ECMP loads calls the out-arcs' edge ids; the loss calls also their per-edge
  *                  and per-vertex loss columns, the outage calls the edges' ends and latencies
  *                  and the self-loop lists, the repricing calls what the outage and the ECMP
- *                  loads calls build); all once per context
+ *                  loads calls build, the edit calls what the repricing calls build); all once
+ *                  per context
  *   scratch growth a call that needs more scratch than the context holds frees the old block
  *                  (which waits for the device) and allocates: shd_route_rows_async under KB
  *                  without fused path attributes and shd_route_fw_rows_async when ns grows,
@@ -53,7 +54,8 @@
  *                  shd_route_loads_async, shd_route_fold_async, shd_route_ties_async,
  *                  shd_route_ecmp_loads_async, shd_route_loss_async, shd_route_outage_async and
  *                  shd_route_reprice_async in their HBM forms when the slices grow (those
- *                  synchronise the stream)
+ *                  synchronise the stream); shd_route_edit_async follows shd_route_reprice_async
+ *                  in both
  * A first call with the largest sizes takes both out of the way.
  * Capture: after such a first call, shd_route_rows_async (every kernel),
  * shd_route_rows_planned_async (with and without SHD_ROUTE_PLAN_REUSE),
@@ -94,6 +96,8 @@
  *   shd_route_outage, shd_route_pair_outage, shd_route_reprice, shd_route_pair_reprice <- (no
  *                         reference equivalent; what-if scenarios that remove links or change
  *                         their latencies)
+ *   shd_route_edit, shd_route_pair_edit <- (no reference equivalent; what-if scenarios that
+ *                         remove links, change their latencies and add links in one step)
  *
  * Semantics of one (s,t) entry are exactly the Path the reference would cache:
  *   t != s : lat = 0.0 + sum of edge latencies along the chosen shortest path, summed
@@ -697,6 +701,95 @@ int shd_route_pair_reprice(shd_route_t* ctx, const int32_t* pair_src, const int3
                            const int32_t* scn_edge, const double* scn_lat, int32_t nscn, uint64_t* stats_out,
                            double* max_add_out, double* max_gain_out, double* min_new_out, double* lat_out,
                            uint64_t* unrouted_out);
+
+/* ---- link edits: what the entries gain or lose when links are removed, repriced and added ----
+ * No reference equivalent: a user of Shadow 1.14 loads another topology.
+ * Scenario k is the list of records (scn_edge[x], scn_a[x], scn_b[x], scn_lat[x]) for x in
+ * scn_off[k] .. scn_off[k+1)):
+ *   scn_edge[x] >= 0 with a finite scn_lat[x] > 0 gives that edge id this latency, as the
+ *     repricing calls do;
+ *   scn_edge[x] >= 0 with scn_lat[x] == +inf removes that edge, as the outage calls do;
+ *     for both, scn_a[x] and scn_b[x] are ignored;
+ *   scn_edge[x] == -1 is a new link between scn_a[x] and scn_b[x] at latency scn_lat[x],
+ *     undirected or directed as the graph is (a directed graph gets the one arc a -> b); its
+ *     latency must be finite and > 0; several new links between the same ends are allowed.
+ * G_k is the context's graph with the removed edges taken out and the others in their order,
+ * the repriced latencies replaced and the new links appended behind every existing edge in list
+ * order, so that their ids lie above every existing id.  Losses play no part: no reliability is
+ * computed.
+ *   SHD_ROUTE_EINVAL for the whole call, nothing written: an id outside [0, n_edges) other than
+ * -1; an id repeated within one scenario; a NaN, zero or negative latency, or +inf on a new link;
+ * an end of a new link outside [0, n_vertices); scn_a[x] == scn_b[x] on a new link (a new
+ * self-loop could only become the self entry of a vertex whose entry fails in G or whose own
+ * loops were all removed; it stays out of scope).
+ *   Absorbed latencies follow the rule at shd_graph_t: with lo the minimum and hi the maximum
+ * over the graph's latencies on edges that are no self-loops, every finite new latency put on
+ * such an edge and every new link's latency, lo <= (n_vertices - 1) * hi * 2^-52 makes the whole
+ * call SHD_ROUTE_EUNSUPPORTED with nothing computed, as for the repricing calls (sufficient for
+ * every G_k at once and therefore conservative).
+ *   Every entry is judged without dispatch: flags must be 0, any bit is SHD_ROUTE_EINVAL.
+ *   old = the entry in G.  An entry that fails in G (SHD_ROUTE_ENOEDGE, SHD_ROUTE_EUNREACH) raises
+ * its code, adds its weight to *unrouted once and takes part in no scenario.  This is a limit: an
+ * entry that fails in G stays out even where a new link of the scenario would route it.
+ *   new = the entry of a context created from G_k: for t != s the shortest latency in G_k (the
+ * f64 left fold from the source), for t == s the latency in G_k of the lowest-id self-loop of s
+ * that is not removed.
+ *   Per scenario, stats[k*SHD_ROUTE_EDIT_NSTAT + ...] in u64 adds, exact mod 2^64 and independent
+ * of order:
+ *     SHD_ROUTE_EDIT_HIT     the weight of the entries whose old route, the one shd_route_paths
+ *                            reports, uses a removed or repriced edge (for a self entry: the
+ *                            lowest self-loop);
+ *     SHD_ROUTE_EDIT_CUT     the weight of the entries with no route in G_k;
+ *     SHD_ROUTE_EDIT_SLOWER  the weight of the entries routable in both with new > old;
+ *     SHD_ROUTE_EDIT_FASTER  the weight of the entries with new < old;
+ * max_add[k] and max_gain[k] as for the repricing calls (u64 maxima on the bits, 0.0 without an
+ * entry of the kind); min_new[k] = the smallest new latency over the entries routable in G and in
+ * G_k (a u64 minimum on the bits, +inf without one).  lat[(k*ns + i)*ld + j], if asked for, is
+ * the new latency, NaN where the entry is cut or failed in G; it is bit-equal to lat of
+ * shd_route_rows with flags 0 on a context created from G_k.  An entry whose only change is a
+ * tied alternative through a new link keeps its latency and counts nowhere.
+ *   nscn == 0 writes only *unrouted; an empty scenario gives zero stats, the old latencies and
+ * the old minimum.
+ *   The calls run a rows launch inside and follow the repricing calls' scratch, work units and
+ * state: the same 21.25 / 29.25 bytes per vertex, in LDS up to 7,456 vertices or, on larger
+ * graphs and with SHD_ROUTE_EDIT_LDS=0, in HBM slices.  A unit finds the scenarios that touch a
+ * parent arc or the source's lowest self-loop, or lower an edge below the distance gap of its
+ * ends, or whose new link does (every other scenario leaves the row as it is), marks the subtrees
+ * below the listed tree arcs, rebuilds them with a listed arc at its listed latency and a removed
+ * arc left out, then pushes what fell along the out-arcs and along every new link of the
+ * scenario, round by round, until a round lowers nothing.  Known limits: a
+ * scenario's whole list of new links is relaxed in every round, and the live test and the id
+ * searches are the repricing calls'.  Diagnostic rate: every call runs the sources' SSSP. */
+#define SHD_ROUTE_EDIT_HIT 0
+#define SHD_ROUTE_EDIT_CUT 1
+#define SHD_ROUTE_EDIT_SLOWER 2
+#define SHD_ROUTE_EDIT_FASTER 3
+#define SHD_ROUTE_EDIT_NSTAT 4
+/* Device pointers, as shd_route_reprice_async, with d_scn_a and d_scn_b beside d_scn_edge.  Each
+ * scenario holds its new links first, in any order, then its ids strictly ascending.  A
+ * validation kernel raises SHD_ROUTE_EINVAL on the error word for an offset, id, order, end or
+ * latency violation and SHD_ROUTE_EUNSUPPORTED for the absorbed-latency rule (the outputs are
+ * then undefined); the main kernel indexes no memory with an unchecked id or end. */
+int shd_route_edit_async(shd_route_t* ctx, const int32_t* d_src, int32_t ns, const int32_t* d_tgt,
+                         int32_t nt, int64_t ld, uint32_t flags, const uint64_t* d_wt,
+                         const int64_t* d_scn_off, const int32_t* d_scn_edge, const int32_t* d_scn_a,
+                         const int32_t* d_scn_b, const double* d_scn_lat, int32_t nscn, uint64_t* d_stats,
+                         double* d_max_add, double* d_max_gain, double* d_min_new, double* d_lat,
+                         uint64_t* d_unrouted, void* stream);
+/* Same with host pointers (row stride nt); blocks.  Records in any order: each scenario is sorted
+ * inside, new links first in the caller's order, then ids ascending. */
+int shd_route_edit(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt, int32_t nt,
+                   uint32_t flags, const uint64_t* wt, const int64_t* scn_off, const int32_t* scn_edge,
+                   const int32_t* scn_a, const int32_t* scn_b, const double* scn_lat, int32_t nscn,
+                   uint64_t* stats_out, double* max_add_out, double* max_gain_out, double* min_new_out,
+                   double* lat_out, uint64_t* unrouted_out);
+/* The sparse form: npairs (pair_src[p], pair_tgt[p], pair_wt[p]) in any order (pair_wt NULL =
+ * 1 each); lat_out[k*npairs + p] in the caller's pair order.  Host pointers; blocks. */
+int shd_route_pair_edit(shd_route_t* ctx, const int32_t* pair_src, const int32_t* pair_tgt,
+                        const uint64_t* pair_wt, int64_t npairs, uint32_t flags, const int64_t* scn_off,
+                        const int32_t* scn_edge, const int32_t* scn_a, const int32_t* scn_b,
+                        const double* scn_lat, int32_t nscn, uint64_t* stats_out, double* max_add_out,
+                        double* max_gain_out, double* min_new_out, double* lat_out, uint64_t* unrouted_out);
 
 /* Direct-path pairs (topology.c:1877-1927) for the full src x tgt block. */
 int shd_route_direct(shd_route_t* ctx, const int32_t* src, int32_t ns, const int32_t* tgt,

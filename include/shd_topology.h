@@ -215,6 +215,24 @@ int shd_topology_link_outage(shd_topology_t* top, const int64_t* scn_off, const 
 int shd_topology_link_reprice(shd_topology_t* top, const int64_t* scn_off, const int32_t* scn_edge,
                               const double* scn_lat, int32_t nscn, uint64_t* stats, double* max_add,
                               double* max_gain, double* min_new, uint64_t* unrouted);
+/* What the same pairs and counters gain or lose when links are removed, repriced and added in one
+ * scenario: the records (scn_edge[x], scn_a[x], scn_b[x], scn_lat[x]) of shd_route_pair_edit in
+ * shd_route.h, in any order -- an edge id with a finite latency reprices it, with +inf removes it,
+ * the id -1 adds a link between scn_a[x] and scn_b[x].  stats[nscn * SHD_ROUTE_EDIT_NSTAT] = per
+ * scenario the packets whose route used a removed or repriced link, those that are cut off, those
+ * that get slower and those that get faster; max_add, max_gain, min_new and *unrouted as for
+ * shd_topology_link_reprice.  The counted pairs are taken in the stored orientation (lower ->
+ * higher vertex).  Same rules: a dispatching cache is SHD_ROUTE_EUNSUPPORTED, whatever
+ * shd_route_pair_edit refuses as SHD_ROUTE_EINVAL is refused here with nothing written (before the
+ * first fill too; a repeated id costs a sort of the scenario's ids), engine 0 under the lock,
+ * nothing cached, stats and maxima zero and min_new +inf before the first fill; each output may
+ * be NULL.  "Nothing written" covers SHD_ROUTE_EINVAL only: the absorbed-latency refusal
+ * (SHD_ROUTE_EUNSUPPORTED) comes from the engine call, which needs counted pairs, and arrives
+ * after the outputs were set to zero and +inf, as for shd_topology_link_reprice. */
+int shd_topology_link_edit(shd_topology_t* top, const int64_t* scn_off, const int32_t* scn_edge,
+                           const int32_t* scn_a, const int32_t* scn_b, const double* scn_lat, int32_t nscn,
+                           uint64_t* stats, double* max_add, double* max_gain, double* min_new,
+                           uint64_t* unrouted);
 /* ---- path folds: a per-link quantity along the stored Paths ---------------------------------
  * No reference equivalent (shd_route_pair_fold in shd_route.h).  Like the route calls above
  * these run on engine 0 under the topology lock, compute on demand (diagnostic rate), cache

@@ -1470,3 +1470,8 @@ extern "C" int shd_route_debug_buffer(shd_route_t* c, void* d_buf) {
     return SHD_ROUTE_OK;
 }
 #endif
+
+// The link edit calls and their kernels (link_edit.hpp) stand behind everything else of the code
+// object, so that no kernel the other calls share moves.
+#include "link_edit.hpp"
+#include "edit_calls.hpp"

@@ -155,7 +155,7 @@ DevTies dev_ties(const shd_route* c) {
 
 // the buffers grown on demand (shd_route_destroy; the uploads are in the context's allocs)
 void path_free(PathDev& p) {
-    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.lo_ws.p, p.ou_ws.p, p.rp_ws.p, p.buf})
+    for (char* q : {p.hp_ws.p, p.ld_ws.p, p.ti_ws.p, p.ec_ws.p, p.fo_ws.p, p.lo_ws.p, p.ou_ws.p, p.rp_ws.p, p.ed_ws.p, p.buf})
         if (q) (void)hipFree(q);
 }
 

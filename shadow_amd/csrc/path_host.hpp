@@ -98,7 +98,7 @@ inline ScratchChunks scratch_chunks(int n, int count, size_t budget, bool hrow) 
 
 // ---- the form of a per-source state kernel ----
 // hops_depth_kernel, loads_tree_kernel, fold_tree_kernel, loss_tree_kernel, ties_dag_kernel,
-// ecmp_dag_kernel, outage_repair_kernel and reprice_kernel (k = their work units) keep one source's state per
+// ecmp_dag_kernel, outage_repair_kernel, reprice_kernel and edit_kernel (k = their work units) keep one source's state per
 // workgroup:
 // none under dispatch on a complete graph (mode 2: no tree; such a graph has n <= 65535, its
 // edge count being an int), else u16 state in LDS while it fits and the knob does not say off,
@@ -176,6 +176,11 @@ struct PathDev {
     double rp_lo = 0.0, rp_hi = 0.0;
     unsigned long long* rp_lohi = nullptr;
     PathSlices rp_ws;
+    // link edits: the dynamic-LDS limit of the LDS form is raised, the two words the check
+    // kernel reduces into, set at the first edit call; and the HBM slices
+    int ed_ready = 0;
+    unsigned long long* ed_lohi = nullptr;
+    PathSlices ed_ws;
 };
 
 }  // namespace shd

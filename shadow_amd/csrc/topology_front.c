@@ -931,6 +931,67 @@ int shd_topology_link_reprice(shd_topology_t* t, const int64_t* scn_off, const i
     return rc;
 }
 
+/* ---- link edits over the stored Paths (shd_route_pair_edit on engine 0, nothing cached) ---- */
+
+static int edit_id_cmp(const void* a, const void* b) {
+    const int32_t x = *(const int32_t*)a, y = *(const int32_t*)b;
+    return (x > y) - (x < y);
+}
+
+int shd_topology_link_edit(shd_topology_t* t, const int64_t* scn_off, const int32_t* scn_edge, const int32_t* scn_a,
+                           const int32_t* scn_b, const double* scn_lat, int32_t nscn, uint64_t* stats,
+                           double* max_add, double* max_gain, double* min_new, uint64_t* unrouted) {
+    if (!t || nscn < 0 || (nscn && !scn_off)) return SHD_ROUTE_EINVAL;
+    if (t->complete || t->prefer_direct) return SHD_ROUTE_EUNSUPPORTED;  /* the cache dispatches */
+    if (nscn && (scn_off[0] != 0 || (scn_off[nscn] && (!scn_edge || !scn_lat)))) return SHD_ROUTE_EINVAL;
+    int64_t longest = 0;
+    for (int32_t k = 0; k < nscn; k++) {
+        if (scn_off[k + 1] < scn_off[k]) return SHD_ROUTE_EINVAL;
+        if (scn_off[k + 1] - scn_off[k] > longest) longest = scn_off[k + 1] - scn_off[k];
+    }
+    /* everything that is SHD_ROUTE_EINVAL is judged here, before an output is touched and whether or
+     * not a pair is counted yet; a repeated id through a sorted copy of the scenario's ids */
+    int32_t* ids = longest > 1 ? malloc(sizeof(int32_t) * (size_t)longest) : NULL;
+    if (longest > 1 && !ids) return SHD_ROUTE_ENOMEM;
+    int bad = 0;
+    for (int32_t k = 0; k < nscn && !bad; k++) {
+        int64_t ni = 0;
+        for (int64_t x = scn_off[k]; x < scn_off[k + 1] && !bad; x++) {
+            if (scn_edge[x] < -1 || scn_edge[x] >= t->g.n_edges || !(scn_lat[x] > 0.0)) bad = 1;
+            else if (scn_edge[x] == -1)
+                bad = !scn_a || !scn_b || isinf(scn_lat[x]) || scn_a[x] < 0 || scn_a[x] >= t->g.n_vertices ||
+                      scn_b[x] < 0 || scn_b[x] >= t->g.n_vertices || scn_a[x] == scn_b[x];
+            else if (ids) ids[ni++] = scn_edge[x];
+        }
+        if (bad || ni < 2) continue;
+        qsort(ids, (size_t)ni, sizeof(int32_t), edit_id_cmp);
+        for (int64_t y = 1; y < ni && !bad; y++) bad = ids[y] == ids[y - 1];
+    }
+    free(ids);
+    if (bad) return SHD_ROUTE_EINVAL;
+    for (int64_t k = 0; k < nscn; k++) {
+        if (stats)
+            for (int q = 0; q < SHD_ROUTE_EDIT_NSTAT; q++) stats[k * SHD_ROUTE_EDIT_NSTAT + q] = 0;
+        if (max_add) max_add[k] = 0.0;
+        if (max_gain) max_gain[k] = 0.0;
+        if (min_new) min_new[k] = INFINITY;
+    }
+    if (unrouted) *unrouted = 0;
+    pthread_mutex_lock(&t->lock);
+    int32_t *ps = NULL, *pt = NULL;
+    uint64_t* pw = NULL;
+    size_t np = 0;
+    int rc = counted_pairs(t, &ps, &pt, &pw, &np);
+    if (!rc && np) {
+        rc = shd_route_pair_edit(t->eng[0], ps, pt, pw, (int64_t)np, 0u, scn_off, scn_edge, scn_a, scn_b, scn_lat, nscn,
+                                 stats, max_add, max_gain, min_new, NULL, unrouted);
+        if (rc == SHD_ROUTE_ENOEDGE || rc == SHD_ROUTE_EUNREACH) rc = SHD_ROUTE_OK;  /* as above */
+    }
+    pthread_mutex_unlock(&t->lock);
+    free(ps); free(pt); free(pw);
+    return rc;
+}
+
 /* ---- path folds along the stored Paths (shd_route_pair_fold on engine 0, nothing cached) ---- */
 
 int shd_topology_edge_jitter(shd_topology_t* t, double* out) {

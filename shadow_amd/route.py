@@ -33,6 +33,7 @@ FOLD_SUM, FOLD_MIN, FOLD_MAX, FOLD_PROD = 0, 1, 2, 3  # SHD_ROUTE_FOLD_*
 FOLD_MAX_N = 8
 OUTAGE_HIT, OUTAGE_CUT, OUTAGE_SLOWER, OUTAGE_NSTAT = 0, 1, 2, 3  # SHD_ROUTE_OUTAGE_*
 REPRICE_HIT, REPRICE_SLOWER, REPRICE_FASTER, REPRICE_NSTAT = 0, 1, 2, 3  # SHD_ROUTE_REPRICE_*
+EDIT_HIT, EDIT_CUT, EDIT_SLOWER, EDIT_FASTER, EDIT_NSTAT = 0, 1, 2, 3, 4  # SHD_ROUTE_EDIT_*
 
 
 class RouteError(RuntimeError):
@@ -95,6 +96,7 @@ EXPORTS = (
     "shd_route_loss_async", "shd_route_loss", "shd_route_pair_loss",
     "shd_route_outage_async", "shd_route_outage", "shd_route_pair_outage",
     "shd_route_reprice_async", "shd_route_reprice", "shd_route_pair_reprice",
+    "shd_route_edit_async", "shd_route_edit", "shd_route_pair_edit",
 )
 
 _lib = None
@@ -207,6 +209,12 @@ def load_library():
     L.shd_route_reprice.argtypes = [P, P, I32, P, I32, U32, P, P, P, P, I32, P, P, P, P, P, P]
     L.shd_route_pair_reprice.restype = C.c_int
     L.shd_route_pair_reprice.argtypes = [P, P, P, P, I64, U32, P, P, P, I32, P, P, P, P, P, P]
+    L.shd_route_edit_async.restype = C.c_int
+    L.shd_route_edit_async.argtypes = [P, P, I32, P, I32, I64, U32, P, P, P, P, P, P, I32, P, P, P, P, P, P, P]
+    L.shd_route_edit.restype = C.c_int
+    L.shd_route_edit.argtypes = [P, P, I32, P, I32, U32, P, P, P, P, P, P, I32, P, P, P, P, P, P]
+    L.shd_route_pair_edit.restype = C.c_int
+    L.shd_route_pair_edit.argtypes = [P, P, P, P, I64, U32, P, P, P, P, P, I32, P, P, P, P, P, P]
     L.shd_route_fold_async.restype = C.c_int
     L.shd_route_fold_async.argtypes = [P, P, I32, P, I32, I64, U32, P, I32, P, P, I64, P]
     L.shd_route_fold.restype = C.c_int
@@ -259,6 +267,32 @@ def pack_reprice(scenarios):
     if len(edge) != len(lat):
         raise ValueError("one new latency per listed edge id")
     return off, edge, lat
+
+
+def pack_edits(scenarios):
+    """(off int64, edge int32, a int32, b int32, lat float64) of a list of scenarios, each a list
+    of items -- (edge id, latency) reprices that edge, (edge id, math.inf) removes it, (a, b,
+    latency) adds a link between a and b (edge -1) -- or of an (off, edge, a, b, lat) tuple of
+    arrays."""
+    if isinstance(scenarios, tuple):
+        off = np.ascontiguousarray(scenarios[0], np.int64)
+        edge, a, b = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in scenarios[1:4])
+        lat = np.ascontiguousarray(scenarios[4], np.float64).reshape(-1)
+    else:
+        lists = [[tuple(it) for it in f] for f in scenarios]
+        if any(len(it) not in (2, 3) for f in lists for it in f):
+            raise ValueError("an item is (edge id, latency) or (a, b, latency)")
+        off = np.zeros(len(lists) + 1, np.int64)
+        if lists:
+            off[1:] = np.cumsum([len(f) for f in lists])
+        items = [it for f in lists for it in f]
+        edge = np.array([it[0] if len(it) == 2 else -1 for it in items], np.int32)
+        a = np.array([0 if len(it) == 2 else it[0] for it in items], np.int32)
+        b = np.array([0 if len(it) == 2 else it[1] for it in items], np.int32)
+        lat = np.array([it[-1] for it in items], np.float64)
+    if not len(edge) == len(a) == len(b) == len(lat):
+        raise ValueError("one id, two ends and one latency per record")
+    return off, edge, a, b, lat
 
 
 def _check(rc, what):
@@ -667,6 +701,59 @@ class RouteEngine:
         _check(rc, "shd_route_pair_reprice")
         return res
 
+    def _edit_out(self, nscn, entries, lat, out):
+        if out is not None:
+            return out
+        return (np.zeros((nscn, EDIT_NSTAT), np.uint64), np.zeros(nscn, np.float64), np.zeros(nscn, np.float64),
+                np.full(nscn, np.inf), np.full((nscn, *entries), np.nan) if lat else None, np.zeros(1, np.uint64))
+
+    def edit(self, sources, targets, scenarios, weights=None, lat: bool = False, out=None):
+        """shd_route_edit: (stats, max_add, max_gain, min_new, lat, unrouted) of the (source,
+        target) block under every scenario, each a list of items as pack_edits() takes them:
+        (edge id, latency) reprices, (edge id, math.inf) removes, (a, b, latency) adds a link.
+        stats is uint64 (scenarios, EDIT_NSTAT) with the columns EDIT_HIT, EDIT_CUT, EDIT_SLOWER
+        and EDIT_FASTER; the rest as reprice(), lat NaN where the entry is cut or fails in the
+        graph itself."""
+        s = np.ascontiguousarray(sources, np.int32)
+        t = np.ascontiguousarray(targets, np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint64)
+        if w is not None and w.shape != (len(s), len(t)):
+            raise ValueError("weights must be (sources, targets)")
+        off, edge, a, b, nl = pack_edits(scenarios)
+        nscn = len(off) - 1
+        st, mx, mg, mn, la, un = self._edit_out(nscn, (len(s), len(t)), lat, out)
+        rc = load_library().shd_route_edit(self._h, _p(s), len(s), _p(t), len(t), 0, _p(w), _p(off), _p(edge), _p(a),
+                                           _p(b), _p(nl), nscn, _p(st), _p(mx), _p(mg), _p(mn), _p(la), _p(un))
+        res = (st, mx, mg, mn, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_edit")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_edit")
+        return res
+
+    def pair_edit(self, pair_src, pair_tgt, scenarios, pair_wt=None, lat: bool = False, out=None):
+        """shd_route_pair_edit: as edit() for a list of (source, target, weight) pairs in any
+        order, repeats adding up (pair_wt None = 1 each); lat is (scenarios, pairs) in the
+        caller's pair order."""
+        s = np.ascontiguousarray(pair_src, np.int32)
+        t = np.ascontiguousarray(pair_tgt, np.int32)
+        w = None if pair_wt is None else np.ascontiguousarray(pair_wt, np.uint64)
+        if len(s) != len(t) or (w is not None and len(w) != len(s)):
+            raise ValueError("pair_src, pair_tgt and pair_wt differ in length")
+        off, edge, a, b, nl = pack_edits(scenarios)
+        nscn = len(off) - 1
+        st, mx, mg, mn, la, un = self._edit_out(nscn, (len(s),), lat, out)
+        rc = load_library().shd_route_pair_edit(self._h, _p(s), _p(t), _p(w), len(s), 0, _p(off), _p(edge), _p(a), _p(b),
+                                                _p(nl), nscn, _p(st), _p(mx), _p(mg), _p(mn), _p(la), _p(un))
+        res = (st, mx, mg, mn, la, None if un is None else int(un[0]))
+        if rc in (ENOEDGE, EUNREACH):
+            err = RouteError(rc, "shd_route_pair_edit")
+            err.partial = res
+            raise err
+        _check(rc, "shd_route_pair_edit")
+        return res
+
     def _fold_args(self, ops, values):
         o = np.ascontiguousarray(ops, np.int32).reshape(-1)
         v = np.ascontiguousarray(values, np.float64)
@@ -758,6 +845,22 @@ class RouteEngine:
             ptr(d_scn_lat), nscn, ptr(d_stats), ptr(d_max_add), ptr(d_max_gain), ptr(d_min_new), ptr(d_lat),
             ptr(d_unrouted), C.c_void_p(stream) if stream else None)
         _check(rc, "shd_route_reprice_async")
+
+    def edit_async(self, d_src, d_tgt, d_wt, d_scn_off, d_scn_edge, d_scn_a, d_scn_b, d_scn_lat, d_stats, d_max_add,
+                   d_max_gain, d_min_new, d_lat, d_unrouted, stream=None, ld=None, flags=0):
+        """shd_route_edit_async over device tensors: as reprice_async(), with the int32 ends of
+        the new links beside the edge ids (each scenario its new links, id -1, first and then its
+        ids strictly ascending; +inf removes) and stats of EDIT_NSTAT columns; any output may be
+        None."""
+        ns, nt = int(d_src.numel()), int(d_tgt.numel())
+        ld = nt if ld is None else int(ld)
+        nscn = 0 if d_scn_off is None else int(d_scn_off.numel()) - 1
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = load_library().shd_route_edit_async(
+            self._h, ptr(d_src), ns, ptr(d_tgt), nt, ld, int(flags), ptr(d_wt), ptr(d_scn_off), ptr(d_scn_edge),
+            ptr(d_scn_a), ptr(d_scn_b), ptr(d_scn_lat), nscn, ptr(d_stats), ptr(d_max_add), ptr(d_max_gain),
+            ptr(d_min_new), ptr(d_lat), ptr(d_unrouted), C.c_void_p(stream) if stream else None)
+        _check(rc, "shd_route_edit_async")
 
     def loss_async(self, d_src, d_tgt, d_wt, d_edge_reach, d_edge_drop, d_vertex_drop, d_delivered, d_unrouted,
                    stream=None, dispatch=True, ld=None, add=False):

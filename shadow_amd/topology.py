@@ -33,6 +33,7 @@ EXPORTS = (
     "shd_topology_edge_count", "shd_topology_add_path_packets",
     "shd_topology_edge_jitter", "shd_topology_fold_pairs", "shd_topology_link_loss", "shd_topology_link_outage",
     "shd_topology_link_reprice",
+    "shd_topology_link_edit",
     "shd_topology_tie_stats", "shd_topology_dump_ties", "shd_topology_tie_line", "shd_topology_tie_summary_line",
 )
 
@@ -121,6 +122,8 @@ def load_library():
     L.shd_topology_link_outage.argtypes = [P, P, P, C.c_int32, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_link_reprice.restype = C.c_int
     L.shd_topology_link_reprice.argtypes = [P, P, P, P, C.c_int32, P, P, P, P, C.POINTER(C.c_uint64)]
+    L.shd_topology_link_edit.restype = C.c_int
+    L.shd_topology_link_edit.argtypes = [P, P, P, P, P, P, C.c_int32, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_link_loss.restype = C.c_int
     L.shd_topology_link_loss.argtypes = [P, P, P, P, P, C.POINTER(C.c_uint64)]
     L.shd_topology_edge_jitter.restype = C.c_int
@@ -466,6 +469,28 @@ class Topology:
                                          C.c_void_p(mg.ctypes.data), C.c_void_p(mn.ctypes.data), C.byref(un))
         if rc:
             raise RuntimeError(f"link_reprice failed ({rc})")
+        return st, mx, mg, mn, int(un.value)
+
+    def link_edit(self, scenarios):
+        """shd_topology_link_edit: (stats, max_add, max_gain, min_new, unrouted) of the cached
+        Paths' packet counters under every scenario of items as route.pack_edits() takes them --
+        (edge id, latency) reprices, (edge id, math.inf) removes, (a, b, latency) adds a link --
+        or an (off, edge, a, b, lat) tuple: uint64 stats (scenarios, 4) = the packets hit, cut,
+        slower and faster, the rest as link_reprice().  Raises RuntimeError with
+        SHD_ROUTE_EUNSUPPORTED (-6) for a topology whose cache dispatches."""
+        from .route import pack_edits
+        L = load_library()
+        off, edge, a, b, nl = pack_edits(scenarios)
+        nscn = len(off) - 1
+        st = np.zeros((nscn, 4), np.uint64)
+        mx, mg, mn = np.zeros(nscn, np.float64), np.zeros(nscn, np.float64), np.full(nscn, np.inf)
+        un = C.c_uint64()
+        vp = lambda x: C.c_void_p(x.ctypes.data) if len(x) else None
+        rc = L.shd_topology_link_edit(self._h, C.c_void_p(off.ctypes.data), vp(edge), vp(a), vp(b), vp(nl), nscn,
+                                      C.c_void_p(st.ctypes.data), C.c_void_p(mx.ctypes.data),
+                                      C.c_void_p(mg.ctypes.data), C.c_void_p(mn.ctypes.data), C.byref(un))
+        if rc:
+            raise RuntimeError(f"link_edit failed ({rc})")
         return st, mx, mg, mn, int(un.value)
 
     def edge_jitter(self):
